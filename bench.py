@@ -1,6 +1,7 @@
 """bench.py — molecules/s of one MoleculeSDE pretrain step on N MI355X (one process per GPU).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR     # + DIR/*.npy: the last timed step's results
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -779,6 +780,54 @@ def cpu_baseline(bs=256):
 # Keys every `--gpus N` line carries beside the contract's own (tests/test_host_logic.py asserts them on the launcher path,
 # tools/dp2_gloo_smoke.sh on a real step): configs[2]'s full step timed by the same ranks, the pieces of a DP step, the
 # per-rank spread.
+DUMP_BUDGET_BYTES = 64 * 10**6    # --dump-outputs: all arrays together
+
+
+def snapshot_outputs(trainer, ret):
+    """Host copies of what the last timed step left a caller: the loss it returned, every model's state dict (parameters and
+    buffers, flattened in state-dict order) and the optimiser's Adam moments.  Called right behind the timed loop, before
+    any later mode steps the same trainer again."""
+    import numpy as np
+    loss = ret[0] if isinstance(ret, tuple) else ret
+    torch.cuda.synchronize()
+    out = {"loss": np.asarray([float(loss.detach())], dtype=np.float32)}
+    for name, model in trainer.models.items():
+        vals = [v.detach().reshape(-1).to("cpu", torch.float32 if v.is_floating_point() else torch.float64)
+                for v in model.state_dict().values()]
+        flt = torch.cat([v for v in vals if v.dtype == torch.float32]) if vals else torch.zeros(0)
+        ints = [v for v in vals if v.dtype == torch.float64]
+        out[f"state_{name}"] = flt.numpy()
+        if ints:
+            out[f"state_{name}_counters"] = torch.cat(ints).numpy()
+    out["adam_m"] = trainer.opt.m.detach().cpu().numpy()
+    out["adam_v"] = trainer.opt.v.detach().cpu().numpy()
+    return out
+
+
+def dump_outputs(arrays, path, budget=DUMP_BUDGET_BYTES):
+    """Write each array as path/<name>.npy (float32 / float64), in order, whole while the byte budget lasts; an array that
+    no longer fits is replaced by a fixed, seeded sample of its elements (sorted indices) of the size that still does, and
+    one of which nothing fits is left out.  Returns {file name: elements written}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = budget
+    written = {}
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr).reshape(-1)
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        n = min(arr.size, max(left - 128, 0) // arr.itemsize)        # 128 bytes: the .npy header
+        if n == 0 and arr.size > 0:
+            continue                                                  # the budget is spent: nothing of it fits
+        if n < arr.size:
+            idx = np.sort(np.random.default_rng(0).choice(arr.size, size=n, replace=False))
+            arr = arr[idx]
+            name = f"{name}_sample"
+        np.save(os.path.join(path, name + ".npy"), arr)
+        left -= 128 + arr.nbytes
+        written[name] = int(arr.size)
+    return written
+
+
 DP_LINE_KEYS = ("config2_full", "dp_step_parts_us", "ms_per_step_per_rank", "rccl_ranks_seen", "rank_devices", "dp_backend")
 DP_PART_KEYS = ("graph_us", "allreduce_us", "adam_us", "allreduce_alone_us", "steps")
 
@@ -912,6 +961,9 @@ def main():
     ap.add_argument("--census_only", action="store_true",
                     help="launcher check: start the ranks, count them with one all-reduce, print the line's DP keys and exit "
                          "(runs without a GPU under MSDE_DP_BACKEND=gloo: tests/test_host_logic.py)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline path computed in its last timed step (loss, every "
+                         "model's state dict, Adam moments) as DIR/<name>.npy, at most %d MB in all" % (DUMP_BUDGET_BYTES // 10**6))
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -996,7 +1048,7 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for s in range(steps):
-                fn(items[s % len(items)])
+                ret = fn(items[s % len(items)])
             if world > 1:       # the rank's own finishing time (the per-rank spread of the line); the barrier below then
                 torch.cuda.synchronize()          # waits for the slowest rank, which is what `value` is computed from
                 local_s["last"] = time.perf_counter() - t0
@@ -1006,15 +1058,23 @@ def main():
             local_s.setdefault("last", dt_)
             if world == 1:
                 local_s["last"] = dt_
+            local_s["ret"] = ret if steps > 0 else None      # what the last timed step returned (--dump-outputs)
             return dt_
         finally:
             gc.enable()
 
+    dumped = {}                 # --dump-outputs: host snapshot of the headline mode's last timed step, per mode
+
+    def snap(mode, tr):
+        if a.dump_outputs and rank == 0 and local_s.get("ret") is not None:
+            dumped[mode] = snapshot_outputs(tr, local_s["ret"])
+
     dt_pool = timed(step_fn, pool, a.steps)
+    snap("pool", trainer)
     dt, launch, stream_info = dt_pool, None, None
     dt_local = local_s.get("last", dt_pool)
 
-    def stream_modes(tr, full, pcie_variants=True):
+    def stream_modes(tr, full, pcie_variants=True, headline=True):
         """`--stream` DISTINCT batches, each fed as its raw collated arrays (one device-to-device copy of the resident blob),
         plans and the extended graph built on the device inside the ONE captured graph of trainer `tr`; then the two-bucket
         mode and (pcie_variants) the blobs from pinned host memory.  Which mode is the headline is a FIXED rule, not "the
@@ -1037,6 +1097,8 @@ def main():
         assert ok
         dt_ = timed(lambda blob: tr.step_bucket(bk, blob), blobs, a.steps)
         dtl_ = local_s["last"]
+        if headline and (not full or a.no_pipeline):
+            snap("stream", tr)
         ok, _ = bk.check()
         assert ok
         launch_ = ("ONE hipGraph for all batches: %d distinct batches streamed as raw collated arrays (1 copy each), "
@@ -1057,6 +1119,8 @@ def main():
                 piped_step(None)
             dt_pipe = timed(piped_step, blobs, a.steps)
             dtl_pipe = local_s["last"]
+            if headline and full:
+                snap("stream", tr)
             pipe.step()                       # drain the batch submitted last
             torch.cuda.synchronize()
             assert pipe.check()
@@ -1103,6 +1167,7 @@ def main():
             print(f"[bench] bucket mode failed ({type(exc).__name__}: {exc}); reporting the per-shape-graph mode",
                   file=sys.stderr)
             dt = dt_pool
+            dumped.pop("stream", None)
         finally:
             from moleculesde_amd import hip as _hip
             _hip.clear_row_bounds()
@@ -1119,7 +1184,7 @@ def main():
             args2 = pretrain.readme_args(SDE_coeff_generative_3Dto2D=1, batch_size=a.batch_size, score_kernel=a.score_kernel)
             tr2 = pretrain.Trainer(args2, device)
             tr2.adam_outside_graph = a.debug_dp_path
-            dt2, dtl2, launch2, info2, (bk2, blobs2) = stream_modes(tr2, True, pcie_variants=False)
+            dt2, dtl2, launch2, info2, (bk2, blobs2) = stream_modes(tr2, True, pcie_variants=False, headline=False)
             parts2 = dp_step_parts(tr2, lambda i: tr2.step_bucket(bk2, blobs2[i % len(blobs2)])) if tr2._use_dp() else None
             config2 = {"dt": dt2, "dt_local": dtl2, "launch": launch2, "stream": info2, "dp_step_parts_us": parts2}
             del tr2
@@ -1243,6 +1308,11 @@ def main():
             out["config5_md17"] = config5_md17(device)
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.batch_size)
+        if a.dump_outputs:
+            arrays = dumped.get("stream", dumped.get("pool"))
+            assert arrays is not None, "--dump-outputs: no timed step to dump (--steps 0?)"
+            written = dump_outputs(arrays, a.dump_outputs)
+            print(f"[bench] dumped {len(written)} arrays of the last timed step to {a.dump_outputs}", file=sys.stderr, flush=True)
         print(json.dumps(out), flush=True)
     dp.barrier()
     if torch.distributed.is_initialized():

@@ -5,7 +5,8 @@ Two modes:
     _network_dense) imported by file path with the package __init__ files bypassed -- no stand-ins.
   * verbatim(): stand-in third-party packages (oracle/standins) + /root/reference on sys.path, then
     the normal `from Geom3D.models import ...`.
-The reference never travels to the GPU box: every caller must skip when available() is False.
+  * standins(): the stand-in third-party layer alone (part of this repository: needs no reference).
+The reference never travels to the GPU box: only the golden generators (oracle/make_golden*.py) call genuine() / verbatim().
 """
 import importlib
 import importlib.util
@@ -61,11 +62,20 @@ def genuine():
     return ns
 
 
+def standins():
+    """Put the stand-in third-party packages on sys.path; returns a namespace of the PyG / torch-scatter pieces."""
+    if _STANDINS not in sys.path:
+        sys.path.insert(0, _STANDINS)
+    import torch_geometric.nn as tgnn
+    import torch_geometric.utils as tgu
+    import torch_scatter
+    return types.SimpleNamespace(nn=tgnn, utils=tgu, scatter=torch_scatter)
+
+
 def verbatim():
     """Import the reference packages on the stand-in third-party layer; returns a namespace."""
     assert available()
-    if _STANDINS not in sys.path:
-        sys.path.insert(0, _STANDINS)
+    st = standins()
     if REF_ROOT not in sys.path:
         sys.path.insert(1, REF_ROOT)
     models = importlib.import_module("Geom3D.models")
@@ -79,8 +89,5 @@ def verbatim():
     ns.sde3d2d = importlib.import_module("Geom3D.models.MoleculeSDE.SDE_model_3D_to_2D_node_adj_dense")
     ns.SDE_sparse = importlib.import_module("Geom3D.models.MoleculeSDE.SDE_sparse")
     ns.SDE_dense = importlib.import_module("Geom3D.models.MoleculeSDE.SDE_dense")
-    import torch_geometric.nn as tgnn
-    import torch_geometric.utils as tgu
-    import torch_scatter
-    ns.standins = types.SimpleNamespace(nn=tgnn, utils=tgu, scatter=torch_scatter)
+    ns.standins = st
     return ns

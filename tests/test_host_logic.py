@@ -102,9 +102,7 @@ def test_extend_graph_matches_reference_algorithm_when_available():
     """The reference's extend_graph sequence (dataset_3D.py:18-34) replayed on the stand-in
     spspmm/coalesce (the dataset module itself imports rdkit and cannot be loaded)."""
     from oracle import ref_loader
-    if not ref_loader.available():
-        pytest.skip("/root/reference not present")
-    ref_loader.verbatim()
+    ref_loader.standins()
     import torch_sparse
     from torch_geometric.utils import remove_self_loops
     from moleculesde_amd.batch import extend_graph_index
@@ -328,3 +326,30 @@ def test_bench_gpus_n_starts_its_own_ranks():
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--census_only"], env=env,
                            capture_output=True, text=True, timeout=120)
         assert r.returncode == 2 and "device(s) visible" in r.stderr
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: arrays are written whole while the byte budget lasts, then as a fixed, seeded sample (the
+    same elements on every run) that keeps the total within the budget; only float32 / float64 leave."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = np.arange(10000, dtype=np.float32)
+    arrays = {"loss": np.array([1.5], dtype=np.float32), "state": big, "counters": np.array([3.0, 4.0])}
+    budget = 128 + 4 + 128 + 4 * 5000 + 128 + 16
+    written = bench.dump_outputs(arrays, str(tmp_path / "a"), budget=budget)
+    assert written == {"loss": 1, "state_sample": 5036}      # (budget - 3 headers - loss) / 4 floats
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= budget
+    s = np.load(tmp_path / "a" / "state_sample.npy")
+    assert s.dtype == np.float32 and np.all(np.diff(s) > 0) and set(s.tolist()) <= set(big.tolist())
+    again = bench.dump_outputs(arrays, str(tmp_path / "b"), budget=budget)
+    assert again == written
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    whole = bench.dump_outputs(arrays, str(tmp_path / "c"))
+    assert whole == {"loss": 1, "state": 10000, "counters": 2}
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 10**6
+    with pytest.raises(AssertionError):
+        bench.dump_outputs({"ids": np.arange(3)}, str(tmp_path / "d"))
