@@ -14,7 +14,13 @@
 
 #define DD_GRID(n) dim3((unsigned)(((n) + 255) / 256 > 4096 ? 4096 : ((n) + 255) / 256 < 1 ? 1 : ((n) + 255) / 256))
 
-__device__ __forceinline__ float dd_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+// s = sigmoid(v) and t = 1 - s = sigmoid(-v), each to full relative precision: forming 1 - s in fp32 leaves t stuck at
+// multiples of 2^-24 once s rounds towards 1 (v > ~17), so s (1 - s) and SiLU's second derivative stopped decaying there
+__device__ __forceinline__ void dd_sigmoid2(float v, float& s, float& t) {
+  const float e = expf(-fabsf(v)), a = 1.f / (1.f + e), b = e * a;     // sigmoid(|v|), sigmoid(-|v|)
+  s = v >= 0.f ? a : b;
+  t = v >= 0.f ? b : a;
+}
 
 // kind 0: shifted softplus, order 0..2; kind 1: cosine cutoff 0.5 (cos(pi d / rc) + 1) for d < rc, 0 beyond, order 0..2
 // (p0 = rc); kind 2: reciprocal (order ignored); kind 3: SiLU x sigmoid(x), order 0..2 (painn.py activation);
@@ -26,8 +32,9 @@ __global__ void dd_unary_kernel(const float* __restrict__ x, const int* __restri
     const float v = x[i];
     float r;
     if (kind == 0) {
-      const float s = dd_sigmoid(v);
-      r = order == 0 ? ((v > 20.f ? v : log1pf(expf(v))) - 0.6931471805599453f) : order == 1 ? s : s * (1.f - s);
+      float s, t;
+      dd_sigmoid2(v, s, t);
+      r = order == 0 ? ((v > 20.f ? v : log1pf(expf(v))) - 0.6931471805599453f) : order == 1 ? s : s * t;
     } else if (kind == 1) {
       const float w = 3.14159265358979323846f / p0, a = v * w;
       r = order == 0 ? 0.5f * (cosf(a) + 1.f) : order == 1 ? -0.5f * w * sinf(a) : -0.5f * w * w * cosf(a);
@@ -35,7 +42,8 @@ __global__ void dd_unary_kernel(const float* __restrict__ x, const int* __restri
     } else if (kind == 2) {
       r = 1.f / v;
     } else if (kind == 3) {
-      const float s = dd_sigmoid(v), t = 1.f - s;
+      float s, t;
+      dd_sigmoid2(v, s, t);
       r = order == 0 ? v * s : order == 1 ? s * (1.f + v * t) : s * t * (2.f + v * (t - s));
     } else {
       const float q = sqrtf(v + p0);

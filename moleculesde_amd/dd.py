@@ -100,22 +100,26 @@ def cosine_cutoff(d, cutoff, src):
 
 
 class _Recip(torch.autograd.Function):
+    """1 / x; mask (optional int array, as cosine_cutoff's): 0 where mask < 0, and so is every derivative."""
+
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, mask=None):
         x = _f32(x)
         y = torch.empty_like(x)
-        _call("msde_dd_unary", _p(x), _p(None), x.numel(), 2, 0, 0.0, _p(y), _stream())
+        _call("msde_dd_unary", _p(x), _p(mask), x.numel(), 2, 0, 0.0, _p(y), _stream())
         ctx.save_for_backward(x)
+        ctx.mask = mask
         return y
 
     @staticmethod
     def backward(ctx, g):
         (x,) = ctx.saved_tensors
-        r = _Recip.apply(x)
-        return scale(mul(g, mul(r, r)), -1.0)
+        r = _Recip.apply(x, ctx.mask)
+        return scale(mul(g, mul(r, r)), -1.0), None
 
 
-recip = _Recip.apply
+def recip(x, mask=None):
+    return _Recip.apply(x, mask)
 
 
 class _Mul(torch.autograd.Function):
@@ -401,7 +405,9 @@ class _RowNorm(torch.autograd.Function):
     def backward(ctx, g):
         (v,) = ctx.saved_tensors
         d = _RowNorm.apply(v, ctx.plan)
-        return mul_rows(v, mul(g, recip(d))), None
+        # 1/d masked to 0 on padded slots: with d pinned to 1 there, v g / d would still have the derivative g in v, and
+        # the second differentiation would hand padded rows a gradient (edge_diff's adjoint drops them; other callers need not)
+        return mul_rows(v, mul(g, recip(d, ctx.plan.src))), None
 
 
 row_norm = _RowNorm.apply
