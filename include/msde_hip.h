@@ -676,7 +676,8 @@ int msde_dense_loss_bwd(const float* g_lx, const float* g_la, const float* res_a
 /* ------------------------------------------------------------------ contrastive loss ------- */
 /* do_CL('EBM_node_dot_prod') in both directions + dual_CL — examples/util.py:52-68,76-79.
  * perm1/perm2: the two negative-sample permutations (torch.randperm).  out[0] = loss, out[1] = accuracy.
- * rows [N,3] (p, n1, n2 logits) and inv1/inv2 [N] (inverse permutations) feed the backward. */
+ * rows [N,3] (p, n1, n2 logits; zero behind *rows_dev) and inv1/inv2 [N] (inverse permutations of the valid rows) feed the
+ * backward. */
 int msde_cl_ebm_fwd(const float* X, const float* Y, const int* perm1, const int* perm2, int N, int D,
                     float invT, float* rows, int* inv1, int* inv2, float* out, const int* rows_dev, void* stream);
 int msde_cl_ebm_bwd(const float* X, const float* Y, const int* perm1, const int* perm2,
@@ -722,8 +723,9 @@ int msde_colsum(const float* X, int M, int C, float* out, float* workspace, cons
  * (msde_reduce_slabs_chunks), prefix[count] = total_chunks.  Fixed summation order, like msde_linear_bwd_w. */
 #define MSDE_REDUCE_ROW 8
 int msde_linear_bwd_w_splits(int M, int N, int K);
-/* Grouped form: the split-M GEMMs of many layers in ONE launch (same tile code and splits; slabs bit-identical to the
- * per-layer kernel except for layers with N <= 32 AND K <= 32, see below).
+/* Grouped form: the split-M GEMMs of many layers in ONE launch (same tile code and splits; weight slabs bit-identical to the
+ * per-layer kernel except for layers with N <= 32 AND K <= 32, see below; bias partials bit-identical for the 64 x 64 tiles
+ * only: the 32 x 128 / 128 x 32 tiles sum a column over 8 groups of 4 / 2 groups of 16 rows of a K tile, not 4 groups of 8).
  * msde_linear_bwd_w_describe fills one HOST row of the problem table for a layer and returns the
  * number of workgroups it needs; prefix[p] = workgroups before problem p, prefix[count] = total_blocks.
  * The row also names the layer's TILE SHAPE (outputs are N x K): 64 x 64 (four waves, a 32 x 32 quadrant each); N <= 32 < 64 < K:

@@ -18,12 +18,16 @@ template <int V>
 __global__ void cl_rows_kernel(const float* __restrict__ X, const float* __restrict__ Y, const int* __restrict__ perm1,
                                const int* __restrict__ perm2, int N, const int* __restrict__ Ndev, int cols, int tpr,
                                float invT, float* __restrict__ rows, int* __restrict__ inv1, int* __restrict__ inv2) {
+  const int Ncap = N;
   N = msde_true_rows(N, Ndev);
   using T = typename VecT<V>::type;
   int rpb = blockDim.x / tpr;
   int i = blockIdx.x * rpb + threadIdx.x / tpr;
   int lane = threadIdx.x % tpr;
-  if (i >= N) return;
+  if (i >= N) {                         // logits of padded rows: zero (finite), never stale memory
+    if (i < Ncap && lane == 0) rows[3 * (size_t)i] = rows[3 * (size_t)i + 1] = rows[3 * (size_t)i + 2] = 0.f;
+    return;
+  }
   int j1 = perm1[i], j2 = perm2[i];
   const T* x = reinterpret_cast<const T*>(X) + (size_t)i * cols;
   const T* y = reinterpret_cast<const T*>(Y) + (size_t)i * cols;

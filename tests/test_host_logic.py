@@ -353,3 +353,38 @@ def test_bench_dump_outputs_budget_and_sample(tmp_path):
     assert bench.DUMP_BUDGET_BYTES <= 64 * 10**6
     with pytest.raises(AssertionError):
         bench.dump_outputs({"ids": np.arange(3)}, str(tmp_path / "d"))
+
+
+def test_every_row_bounded_entry_point_has_a_row_bound_test():
+    """Every msde_* entry point that takes a device row count (a `const int*` named *valid* or *_dev, except the step and seed
+    counters), plus the products whose bound rides in msde_rs_desc.m_valid or in a describe row, is a key of BOUNDED in
+    tests/test_gpu_row_bounds.py (read as text: the GPU module is not imported here)."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hdr = open(os.path.join(root, "include", "msde_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    bounded = {"msde_gemm_rs", "msde_gemm_t2", "msde_linear_bwd_w_grouped_ex"}
+    for m in re.finditer(r"\b(msde_\w+)\s*\(([^;{]*?)\)\s*;", hdr, flags=re.S):
+        for prm in m.group(2).split(","):
+            pm = re.match(r"\s*const\s+int\s*\*\s*(\w+)\s*$", prm)
+            if pm and ("valid" in pm.group(1) or pm.group(1).endswith("_dev")) and pm.group(1) not in ("step_dev", "seed_dev"):
+                bounded.add(m.group(1))
+    assert len(bounded) >= 30, sorted(bounded)
+    src = open(os.path.join(root, "tests", "test_gpu_row_bounds.py")).read()
+    body = src[src.index("BOUNDED = {"):]
+    body = body[:body.index("\n}\n")]
+    entries = dict(re.findall(r'^\s*"(msde_\w+)"\s*:\s*\("([^"]*)"', body, flags=re.M))
+    missing = sorted(bounded - set(entries))
+    assert not missing, f"row-bounded entry points without a row-bound test in BOUNDED: {missing}"
+    # each entry names tests that exist: of this file, or `module.py::test` of another test module
+    defined = set(re.findall(r"^def (test_\w+)\(", src, flags=re.M))
+    for name, tests in entries.items():
+        for t in (x.strip() for x in tests.split(",")):
+            m = re.match(r"(test_\w+\.py)::(test_\w+)", t)
+            if m:
+                other = open(os.path.join(root, "tests", m.group(1))).read()
+                assert re.search(r"^def %s\(" % m.group(2), other, flags=re.M), (name, t)
+            else:
+                assert re.match(r"test_\w+", t) and re.match(r"test_\w+", t).group(0) in defined, (name, t)
+    elsewhere = sorted(n for n, t in entries.items() if "::" in t)
+    assert elsewhere == ["msde_plan_row_lists"], f"bounded entry points not swept in test_gpu_row_bounds.py: {elsewhere}"
