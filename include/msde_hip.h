@@ -672,6 +672,40 @@ int msde_dense_loss_bwd(const float* g_lx, const float* g_la, const float* res_a
                         const float* w2, const float* flags, const float* mean_std, const int* mol_ptr,
                         const int* pair_ptr, int B, int ncls, float anneal_power, float scale_x,
                         float scale_adj, const int* nmax_dev, float* gS, float* gZ2, float* gOUT, void* stream);
+/* The 3D->2D reverse-SDE predictor-corrector sampler (node_adj_PC_generation, pretrain_MoleculeSDE_inference_3D_to_2D_VE_VP.py
+ * :96-262, as intended: csrc/dense_pc.hip) on the layout above, one workgroup per molecule.  State x [N, MSDE_DENSE_XP_LD]
+ * (ncls columns used, the rest 0), adj [P] (exactly symmetric), x_mean, adj_mean; each update also writes the next score
+ * evaluation's inputs AC[:, 0:2] = (adj, adj^2) and XC[:, 0:F] = E3 (embedding_3D(h) + both biases, onto which embedding_X(x)
+ * is accumulated).  par [S][4] = {std(t_k), G(t_k), alpha_k, fa_k} per time step (fa: drift f(x) = fa x - x; VE fa = 1,
+ * alpha = 1).  step [2]: device iteration counters (init zeroes them; corrector reads step[0] and writes step[1], the
+ * predictor reads step[1] and writes step[0]): a captured iteration replays with no host work.  Noise: the injected raw
+ * N(0,1) draws in the reference's padded shapes -- nz_init_* [B][Nm][Nm | ncls], nzc_* [iters][n_steps][B][Nm][Nm | ncls],
+ * nzp_* [iters][B][Nm][Nm | ncls]; pairs read the (min(i,j), max(i,j)) entry (gen_noise's triu + transpose), masks applied
+ * here -- or, where NULL, the counter generator keyed by (seed, iteration, draw, molecule, element).  n_steps <= 127,
+ * Nm <= 32. */
+typedef struct msde_dense_pc_params {
+  const int *mol_ptr, *pair_ptr;
+  const float *flags, *par;
+  long long* step;
+  const float* E3;
+  float *XC, *x, *adj, *x_mean, *adj_mean, *AC;
+  float *score_adj, *score_x, *part;   /* corrector scores [P], [N, XP]; per-molecule norms [B][2 + 2 n_steps] */
+  const float *nz_init_adj, *nz_init_x, *nzc_adj, *nzc_x, *nzp_adj, *nzp_x;
+  unsigned long long seed;
+  int B, Nm, ncls, n_steps, S, iters, F, ldxc;
+  float snr, scale_eps;
+} msde_dense_pc_params;
+/* initial state: adj = mask(triu(z,1) + triu(z,1)^T) (prior_sampling_sym), or the caller's symmetric adj_given [B][Nm][Nm]
+ * masked; x = mask(z) */
+int msde_dense_pc_init(const msde_dense_pc_params* p, const float* adj_given, void* stream);
+/* Langevin corrector (two launches): scores -net/std from the edge network's last hidden layer G2 [P, F2] with its
+ * Linear(F2, 1) (w2, b2) and the node network's OUT [N, XP], per-molecule norms, then the batch means and the n_steps steps on
+ * the score of the input state. */
+int msde_dense_pc_corrector(const msde_dense_pc_params* p, const float* G2, int F2, const float* w2, const float* b2,
+                            const float* OUT, void* stream);
+/* reverse-diffusion predictor: x_mean = x - (f(x) - G^2 score), x = x_mean + G z. */
+int msde_dense_pc_predictor(const msde_dense_pc_params* p, const float* G2, int F2, const float* w2, const float* b2,
+                            const float* OUT, void* stream);
 
 /* ------------------------------------------------------------------ contrastive loss ------- */
 /* do_CL('EBM_node_dot_prod') in both directions + dual_CL — examples/util.py:52-68,76-79.

@@ -106,6 +106,9 @@ SIGNATURES = {
     "msde_dense_node_gcn_bwd": [P, I, P, I, P, P, P, P, I, I, P, P, P],
     "msde_dense_loss_fwd": [P, I, P, P, P, P, P, P, P, P, P, I, I, F, F, F, P, P, P, P, P, P],
     "msde_dense_loss_bwd": [P, P, P, P, P, I, P, P, P, P, P, I, I, F, F, F, P, P, P, P, P],
+    "msde_dense_pc_init": [P, P, P],
+    "msde_dense_pc_corrector": [P, P, I, P, P, P, P],
+    "msde_dense_pc_predictor": [P, P, I, P, P, P, P],
     "msde_plan_build": [P, I, P, P, P, P, P, P, P, I, I, I, I, I, I, I] + [P] * 23 + [P],
     "msde_plan_row_lists": [P, P, I, I, P, P, P, P],
     "msde_dd_unary": [P, P, LL, I, I, F, P, P],
@@ -189,6 +192,15 @@ class RsDesc(ctypes.Structure):
 
 RS_AXF_NONE, RS_AXF_AFFINE, RS_AXF_BNBWD, RS_AXF_RELU, RS_VEC_STORE = 0, 1, 2, 4, 8
 RS_STATS_BNFWD, RS_STATS_BNBWD = 1, 2
+
+
+class DensePcParams(ctypes.Structure):
+    """msde_dense_pc_params of include/msde_hip.h (field order and types must match)."""
+    _fields_ = [(n, P) for n in ("mol_ptr", "pair_ptr", "flags", "par", "step", "E3", "XC", "x", "adj", "x_mean", "adj_mean",
+                                 "AC", "score_adj", "score_x", "part", "nz_init_adj", "nz_init_x", "nzc_adj", "nzc_x", "nzp_adj",
+                                 "nzp_x")] + \
+        [("seed", ULL)] + [(n, I) for n in ("B", "Nm", "ncls", "n_steps", "S", "iters", "F", "ldxc")] + \
+        [("snr", F), ("scale_eps", F)]
 
 
 class EdgeLayerParams(ctypes.Structure):

@@ -446,3 +446,70 @@ def score_networks(edge, node, x, adj, flags):
     eye = torch.eye(N, device=dev)
     fm = flags[:, :, None] * flags[:, None, :]
     return S.view(B, N, N) * (1 - eye) * fm, O.view(B, N, -1) * flags[:, :, None]
+
+
+# ------------------------------------------------------------------------------------------------ forward-only evaluation
+class ScoreEval:
+    """Forward-only EdgeScoreNetwork_dense + NodeScoreNetwork_dense for a sampler (no autograd, no torch operator): the
+    same kernels as edge_forward / node_forward on buffers allocated ONCE, so a captured evaluation allocates nothing.
+
+    embedding_3D(h3) + both biases is computed once (E3); an evaluation accumulates embedding_X(x) (x: [N, XP_LD] rows, ncls
+    columns read) onto XC[:, :F], which must hold E3 at that point -- csrc/dense_pc.hip's update kernels write it back after
+    every step (`reset_embedding` does it on the host for a stand-alone call).  Results: G2 [P, F2] (the pair MLP's last hidden
+    layer; its Linear(F2, 1) is folded into the consumer) and OUT [N, XP_LD] (the node network's output)."""
+
+    def __init__(self, model, cfg, h3, flags):
+        dev = h3.device
+        N, P = cfg.N, cfg.P
+        F = h3.size(1)
+        self.cfg, self.F, self.flags = cfg, F, flags
+        self.chans, self.offs = edge_net_shape(model.edge_score_network)
+        self.TE, self.TN = edge_net_tensors(model.edge_score_network), node_net_tensors(model.node_score_network)
+        self.WX, self.ncls = model.embedding_X.weight, model.embedding_X.weight.size(1)
+        self.E3 = _empty(N, F, device=dev)
+        hip.gemm_ex(h3, model.embedding_3D.weight, self.E3, bias=model.embedding_3D.bias, bias2=model.embedding_X.bias)
+        self.XC, self.AC = _empty(N, F + 64, device=dev), _empty(P, AC_LD, device=dev)
+        self.layers = []
+        for C, CO in self.chans:
+            W2 = 2 * C * 32
+            self.layers.append(types.SimpleNamespace(
+                H=_empty(N, W2, device=dev), QK=_empty(N, W2, device=dev), XV=_empty(N, 16 * C, device=dev),
+                xo=_empty(N, 16, device=dev), IN=_empty(P, 2 * C, device=dev), H1=_empty(P, 16, device=dev),
+                H2=_empty(P, 16, device=dev), xcat=_empty(N, 16 * C, device=dev), Hmc=_empty(N, 16, device=dev),
+                st=_edge_struct(self.TE[16 * len(self.layers):16 * len(self.layers) + 16])))
+        f = self.TE[16 * len(self.chans):]
+        self.fdim = f[0].size(1)
+        self.G1, self.G2 = _empty(P, f[0].size(0), device=dev), _empty(P, f[2].size(0), device=dev)
+        self.w2, self.b2 = f[4], f[5]
+        T = self.TN
+        self.XW0 = _empty(N, 16, device=dev)
+        w1, w2 = T[3].size(0), T[5].size(0)
+        self.Z1, self.F1, self.Z2, self.F2 = (_empty(N, w, device=dev) for w in (w1, w1, w2, w2))
+        self.OUT = _empty(N, XP_LD, device=dev)
+
+    def reset_embedding(self):
+        self.XC[:, :self.F].copy_(self.E3)
+
+    def __call__(self, x):
+        cfg, F, AC, flags = self.cfg, self.F, self.AC, self.flags
+        hip.gemm_ex(x[:, :self.ncls], self.WX, self.XC[:, :F], accumulate=True)       # embedding_X(x), onto E3
+        X = self.XC[:, :F]
+        for l, (C, CO) in enumerate(self.chans):
+            t, s = self.TE[16 * l:16 * l + 16], self.layers[l]
+            Fi = X.size(1)
+            hip.gemm_ex(X, t[0], s.H, bias=t[1], act="tanh")
+            hip.gemm_ex(s.H, t[2], s.QK, bias=t[3], groups=2 * C, group_strides=dict(a=32, b=1024, bias=32, c=32), N=32, K=32)
+            hip.gemm_ex(X, t[4], s.XV, b_kmajor=True, groups=C, group_strides=dict(b=Fi * 16, c=16), N=16, K=Fi)
+            _lib.call("msde_dense_edge_layer_fwd", _p(s.QK), _p(s.XV), _p(AC), self.offs[l][0], self.offs[l][1], C, CO, _p(flags),
+                      _p(cfg.mol_ptr), _p(cfg.pair_ptr), ctypes.byref(s.st), cfg.B, cfg.n_max, _p(s.xo), _p(s.IN), _p(s.H1),
+                      _p(s.H2), _p(s.xcat), _p(s.Hmc), hip._stream())
+            X = s.xo
+        f = self.TE[16 * len(self.chans):]
+        hip.gemm_ex(AC[:, :self.fdim], f[0], self.G1, bias=f[1], act="silu")
+        hip.gemm_ex(self.G1, f[2], self.G2, bias=f[3], act="silu")
+        T = self.TN
+        hip.gemm_ex(self.XC[:, :F], T[0], self.XW0, b_kmajor=True, N=16, K=F)
+        _lib.call("msde_dense_node_gcn_fwd", _p(self.XW0), _p(AC), _p(cfg.mol_ptr), _p(cfg.pair_ptr), _p(T[1]), _p(T[2]), cfg.B,
+                  cfg.n_max, ctypes.c_void_p(self.XC.data_ptr() + 4 * F), self.XC.stride(0), hip._stream())
+        node_mlp_forward(self.XC, T[3], T[4], T[5], T[6], T[7], T[8], self.Z1, self.F1, self.Z2, self.F2, self.OUT)
+        return self.G2, self.OUT

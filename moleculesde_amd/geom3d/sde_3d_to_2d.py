@@ -227,6 +227,21 @@ class SDEModel3Dto2D_node_adj_dense(nn.Module):
                                                          nout=num_class_X if noise_on_one_hot else 1)
         self.noise = _nn.DeviceNoise()
 
+    def get_score_fn(self, sde, model, train=True, continuous=True):
+        """SDE_model_3D_to_2D_node_adj_dense.py:68-99 (operator path): score_fn(x, adj, flags, t) = -model(x, adj, flags) / std(t)
+        with std from the SDE's marGINal_prob.  The sampler's fused path evaluates the same score in csrc/dense_pc.hip."""
+        if not train:
+            model.eval()
+        if not isinstance(sde, (VESDE, VPSDE)):
+            raise NotImplementedError(f"SDE class {sde.__class__.__name__} not supported.")
+
+        def score_fn(x, adj, flags, t):
+            if not continuous:
+                raise NotImplementedError("Discrete not supported")
+            std = sde.marGINal_prob(torch.zeros_like(adj), t)[1]
+            return -model(x, adj, flags) / std[:, None, None]
+        return score_fn
+
     def _forward_fused(self, node_3D_repr, data, reduce_mean, anneal_power, pl, dn):
         """Product path: one autograd node, only libmsde_hip kernels (geom3d/dense_head.py)."""
         device = node_3D_repr.device
