@@ -279,3 +279,14 @@ def test_get_score_fused_falls_back_when_unsupported(dev):
         rep = gnn(b.x, b.edge_index, b.edge_attr)
     out = model.get_score_raw(rep, b, b.positions)
     assert out.shape == (48, 3) and torch.isfinite(out).all()
+    # and the fallback computes the score: the fp64 oracle's get_score network output, per molecule
+    o = R.SDEModel2Dto3D_02(emb_dim=32, hidden_dim=32, beta_min=0.1, beta_max=1.0, num_diffusion_timesteps=1000,
+                            beta_schedule=None, SDE_type="VE", use_extend_graph=True)
+    o.load_state_dict({k: v.detach().cpu() for k, v in model.state_dict().items()})
+    o = o.double().eval()
+    ei = b.extended_edge_index.cpu()
+    with torch.no_grad():
+        feats = o._edge_and_node_features(rep.cpu().double(), b.positions.cpu().double(), ei)
+        ref = o.score_network(ei, *feats)["gradient"]
+    for lo, hi in ((0, 8), (8, 48)):
+        assert_close(out[lo:hi], ref[lo:hi], 2e-4, 2e-4 * float(ref[lo:hi].abs().max()), f"fallback score, atoms {lo}..{hi}")

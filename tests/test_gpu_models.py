@@ -10,7 +10,7 @@ from moleculesde_amd import slabs, wcache  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 from oracle import restate as R  # noqa: E402
-from helpers import assert_close, batch_from, disable_dropout, load_golden, record_parity, sub  # noqa: E402
+from helpers import assert_close, batch_from, disable_dropout, fill_like_generator, load_golden, record_parity, sub  # noqa: E402
 
 TOY = dict(emb=16, filters=16, interactions=2, gaussians=51)
 
@@ -1107,14 +1107,7 @@ def test_fused_dense_head_device_noise_statistics(dev):
 
 def _set_parameters_like_generator(net, base):
     """Same deterministic fill as oracle/make_golden_dense_prod.py::set_parameters."""
-    with torch.no_grad():
-        for i, (_, p) in enumerate(net.named_parameters()):
-            gen = torch.Generator().manual_seed(base + i)
-            if p.dim() == 1:
-                p.copy_(torch.rand(p.shape, generator=gen) * 0.6 - 0.3)
-            else:
-                fan = p.shape[1] if p.shape[0] != p.shape[1] else p.shape[0]
-                p.copy_(torch.randn(p.shape, generator=gen) / fan ** 0.5)
+    fill_like_generator(net, base)
 
 
 @pytest.mark.parametrize("fused", [True, False])

@@ -117,13 +117,15 @@ def test_fixture_trajectory(dev, tag, path):
 def _prod_case(case, dev):
     if case == "replicas":
         sizes, bondless = [14] * 10, None
+    elif case == "large":          # the corrector / predictor rows 20..31 and the whole-molecule edge-layer forward
+        sizes, bondless = [32, 23, 17, 21, 2], None
     else:
         sizes, bondless = [2, 20, 7, 13, 5, 17, 9, 11], 2 + 20 + 3      # atom 3 of the third molecule
     b = _batch(sizes, dev, seed=11, bondless=bondless)
     return b, sizes
 
 
-@pytest.mark.parametrize("case", ["replicas", "ragged"])
+@pytest.mark.parametrize("case", ["replicas", "ragged", "large"])
 @pytest.mark.parametrize("sde_type", ["VE", "VP"])
 @pytest.mark.parametrize("n_steps", [1, 3])
 def test_fused_matches_operator_path_production(dev, case, sde_type, n_steps):
@@ -143,6 +145,8 @@ def test_fused_matches_operator_path_production(dev, case, sde_type, n_steps):
     flags, batch, local = pl[8], pl[6], pl[7]
     if case == "ragged":
         assert float(flags.sum()) == sum(sizes) - 1
+    if case == "large":
+        assert Nm == 32 and float(flags.sum()) == sum(sizes)
     ops = S._generate_ops(m, rep, batch, local, flags, B, Nm, ncls, 1000, I, 1e-4, 0.2, 0.9, n_steps, None, None, noises)
     for name, f, o in zip(("x", "adj", "x_mean", "adj_mean"), fused, ops):
         scale = float(o.abs().max())
