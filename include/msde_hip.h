@@ -800,6 +800,15 @@ int msde_silu_dropout_fwd(const float* x, long long n, float p, unsigned long lo
                           const unsigned long long* seed_dev, float* y, void* stream);
 int msde_silu_dropout_bwd(const float* g, const float* x, long long n, float p, unsigned long long seed,
                           const unsigned long long* seed_dev, float* gx, void* stream);
+/* F.dropout(h, p) after every GIN layer (molecule_gnn_model.py:187-192) on an [M, D] fp32 tensor: keep = uniform(seed',
+ * row * D + col) >= p, kept values scaled by 1/(1-p), with seed' = seed + layer_mix(layer) [+ seed_dev[0]*FNV] (the
+ * silu_dropout convention plus a per-layer offset, so every layer of one step draws its own mask).  The mask is never
+ * stored: the backward applies the same function to the gradient.  Rows at or past row_bound[0] (the true row count on
+ * the device; NULL = all M rows) are not touched.  In place (y == x, gx == g) or out of place.  p in [0, 1). */
+int msde_dropout_rows_fwd(const float* x, int M, int D, const int* row_bound, float p, unsigned long long seed, int layer,
+                          const unsigned long long* seed_dev, float* y, void* stream);
+int msde_dropout_rows_bwd(const float* g, int M, int D, const int* row_bound, float p, unsigned long long seed, int layer,
+                          const unsigned long long* seed_dev, float* gx, void* stream);
 /* out = a*b + c (SDE_model_2D_to_3D.py:393); ga = g*b, gb = g*a (either may be NULL); gc = g. */
 int msde_mul_add_fwd(const float* a, const float* b, const float* c, long long n, float* out, void* stream);
 int msde_mul_add_bwd(const float* g, const float* a, const float* b, long long n, float* ga, float* gb,
@@ -918,6 +927,24 @@ int msde_escore_mol_bwd(const void* const* params, const float* x0, const float*
                         int hidden_coff, int n_max, float p_att, float p_ffn, unsigned long long seed0,
                         const unsigned long long* seed_dev, float eps1, float eps2, const float* saved,
                         const float* g_out, float* g_x0, float* g_edge_attr, int ld_gea, float* slabs, void* stream);
+
+/* ------------------------------------------------------------------ MoleculeNet head ------- */
+/* examples/finetune_MoleculeNet.py:120-137 on the ragged layout (molecule b owns rows mol_ptr[b] .. mol_ptr[b+1] of h [M, D],
+ * row stride ldh; any molecule size, any T >= 1, D <= 16384).  Rows at or past row_bound[0] (the true row count on the
+ * device; NULL = all M rows) contribute nothing.  Fixed-order reductions, no atomics: bitwise repeatable.
+ *   msde_molnet_head_fwd: pool [B, D] = global_mean_pool(h) (an empty molecule pools to 0), logits [B, T] = pool W^T + bias
+ *     (W [T, D] row-major, bias may be NULL).  One launch.
+ *   msde_molnet_bce: the masked multi-task BCEWithLogitsLoss in fp64 on logits and labels y [B, T] in {-1, 0, +1} (0 = missing):
+ *     loss_mat [B, T] (may be NULL), stats[3] = {sum loss_mat / number of valid labels (0/0 = NaN, as the reference), number of
+ *     valid labels, number of NaN logits}, dlogits [B, T] = d loss / d logits in fp32 (may be NULL).  One launch.
+ *   msde_molnet_head_bwd: dh = (dlogits W)[mol(row)] / n_mol for the rows below the bound, 0 for every other row of the M
+ *     rows.  One launch; dW = dlogits^T pool and db = column sums of dlogits are ordinary weight gradients. */
+int msde_molnet_head_fwd(const float* h, int ldh, int M, int D, const int* mol_ptr, int B, const int* row_bound,
+                         const float* W, const float* bias, int T, float* pool, float* logits, void* stream);
+int msde_molnet_bce(const float* logits, const float* y, int B, int T, double* loss_mat, double* stats, float* dlogits,
+                    void* stream);
+int msde_molnet_head_bwd(const float* dlogits, int B, int T, const float* W, int D, const int* mol_ptr,
+                         const int* row_bound, int M, float* dh, int ldh, void* stream);
 
 /* ------------------------------------------------------------------ optimiser -------------- */
 /* torch.optim.Adam step over a flat parameter buffer with per-element lr via segment table —

@@ -143,6 +143,11 @@ SIGNATURES = {
     "msde_ssp_bwd": [P, P, LL, P, P],
     "msde_silu_dropout_fwd": [P, LL, F, ULL, P, P, P],
     "msde_silu_dropout_bwd": [P, P, LL, F, ULL, P, P, P],
+    "msde_dropout_rows_fwd": [P, I, I, P, F, ULL, I, P, P, P],
+    "msde_dropout_rows_bwd": [P, I, I, P, F, ULL, I, P, P, P],
+    "msde_molnet_head_fwd": [P, I, I, I, P, I, P, P, P, I, P, P, P],
+    "msde_molnet_bce": [P, P, I, I, P, P, P, P],
+    "msde_molnet_head_bwd": [P, I, I, P, I, P, P, I, P, I, P],
     "msde_mul_add_fwd": [P, P, P, LL, P, P],
     "msde_mul_add_bwd": [P, P, P, LL, P, P, P],
     "msde_pc_corrector": [P, P, P, P, P, ULL, I, F, F, P, P, P],

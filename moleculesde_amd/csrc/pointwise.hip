@@ -70,6 +70,25 @@ silu_dropout_bwd_kernel(const float* __restrict__ g, const float* __restrict__ x
   }
 }
 
+// y = x * keep / (1 - p) on the rows below the row bound of an [M, D] tensor: F.dropout after a GIN layer
+// (molecule_gnn_model.py:187-192).  keep depends only on (seed', element index), so the backward is the same map applied
+// to the gradient.  seed' = seed + DR_LAYER_MIX * (layer + 1) [+ seed_dev[0] * FNV]; the host mirror is
+// moleculesde_amd.finetune_molnet.dropout_keep_mask.
+#define DR_LAYER_MIX 0xD1B54A32D192ED69ull
+__global__ void __launch_bounds__(256)
+dropout_rows_kernel(const float* x, long long n_cap, int D, const int* __restrict__ row_bound, float p,
+                    unsigned long long seed, int layer, const unsigned long long* __restrict__ seed_dev,
+                    float* y) {     // (x == y allowed: no __restrict__)
+  seed += DR_LAYER_MIX * (unsigned long long)(layer + 1);
+  if (seed_dev) seed += seed_dev[0] * 0x100000001B3ull;
+  const long long n = row_bound ? min(n_cap, (long long)max(row_bound[0], 0) * D) : n_cap;
+  const float scale = 1.f / (1.f - p);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    float v = x[i];
+    y[i] = (p == 0.f || msde_uniform(seed, (unsigned long long)i) >= p) ? v * scale : 0.f;
+  }
+}
+
 // out = a * b + c   (edge_attr = invariant * edge_2D + frame_invariant, SDE_model_2D_to_3D.py:393)
 __global__ void __launch_bounds__(256)
 mul_add_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ c, long long n,
@@ -300,6 +319,24 @@ extern "C" int msde_silu_dropout_bwd(const float* g, const float* x, long long n
               gx);
   MSDE_CHECK_LAUNCH();
   return 0;
+}
+static int dropout_rows(const float* x, int M, int D, const int* row_bound, float p, unsigned long long seed, int layer,
+                        const unsigned long long* seed_dev, float* y, void* stream) {
+  if (M < 0 || D < 0 || !x || !y || !(p >= 0.f && p < 1.f)) return MSDE_EINVAL;
+  long long n = (long long)M * D;
+  if (n == 0) return 0;
+  MSDE_LAUNCH(dropout_rows_kernel, dim3(pw_blocks(n, 1)), dim3(256), 0, as_stream(stream), x, n, D, row_bound, p, seed,
+              layer, seed_dev, y);
+  MSDE_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int msde_dropout_rows_fwd(const float* x, int M, int D, const int* row_bound, float p, unsigned long long seed,
+                                     int layer, const unsigned long long* seed_dev, float* y, void* stream) {
+  return dropout_rows(x, M, D, row_bound, p, seed, layer, seed_dev, y, stream);
+}
+extern "C" int msde_dropout_rows_bwd(const float* g, int M, int D, const int* row_bound, float p, unsigned long long seed,
+                                     int layer, const unsigned long long* seed_dev, float* gx, void* stream) {
+  return dropout_rows(g, M, D, row_bound, p, seed, layer, seed_dev, gx, stream);
 }
 extern "C" int msde_mul_add_fwd(const float* a, const float* b, const float* c, long long n, float* out, void* stream) {
   if (n < 0 || !a || !b || !c || !out) return MSDE_EINVAL;

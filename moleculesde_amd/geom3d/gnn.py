@@ -39,6 +39,11 @@ class GINConv(nn.Module):
 
 
 class GNN(nn.Module):
+    # Opt-in (finetune_molnet.MoleculeNetTrainer sets it): (seed, seed_dev) -- the dropout after every layer runs on
+    # hip.dropout_rows with a mask drawn from (seed, layer, seed_dev[0] when not None, element index) instead of F.dropout.
+    # None (the default): F.dropout, as the reference.
+    device_dropout = None
+
     def __init__(self, num_layer, emb_dim, JK="last", drop_ratio=0, gnn_type="gin", atom_feature_dims=None,
                  bond_feature_dims=None):
         super().__init__()
@@ -99,7 +104,11 @@ class GNN(nn.Module):
                 h = self.gnns[layer](h_list[layer], pl.bond, pl.bond_codes)
                 h = self.batch_norms[layer](h)             # ReLU fused for all but the last layer
             if self.drop_ratio > 0:
-                h = F.dropout(h, self.drop_ratio, training=self.training)
+                if self.device_dropout is None:
+                    h = F.dropout(h, self.drop_ratio, training=self.training)
+                elif self.training:
+                    seed, seed_dev = self.device_dropout
+                    h = hip.dropout_rows(h, self.drop_ratio, seed, layer, seed_dev)
             h_list.append(h)
 
         if self.JK == "concat":

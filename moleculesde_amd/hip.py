@@ -1633,6 +1633,88 @@ def silu_dropout(x, p=0.0, seed=0, seed_dev=None):
     return _SiluDropout.apply(x, p, seed, seed_dev)
 
 
+class _DropoutRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p, seed, layer, seed_dev, row_bound):
+        x = _f32(x)
+        M, D = x.shape
+        y = torch.empty_like(x) if row_bound is None else x.clone()     # (rows past the bound keep their values)
+        ctx.cfg = (M, D, row_bound, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(layer), seed_dev)
+        _lib.call("msde_dropout_rows_fwd", _p(x), M, D, _p(row_bound), float(p), ctx.cfg[4], int(layer), _p(seed_dev), _p(y),
+                  _stream())
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        M, D, row_bound, p, seed, layer, seed_dev = ctx.cfg
+        g = _f32(g)
+        gx = torch.empty_like(g) if row_bound is None else g.clone()
+        _lib.call("msde_dropout_rows_bwd", _p(g), M, D, _p(row_bound), p, seed, layer, _p(seed_dev), _p(gx), _stream())
+        return gx, None, None, None, None, None
+
+
+def dropout_rows(x, p, seed=0, layer=0, seed_dev=None, row_bound=None):
+    """F.dropout(x, p) on an [M, D] tensor (training mode) as one kernel: the keep mask is a function of (seed, layer,
+    seed_dev[0] when given, row * D + col) and is regenerated in the backward, never stored.  row_bound: device int32 scalar
+    with the true row count (rows past it pass through unchanged).  Host mirror: finetune_molnet.dropout_keep_mask."""
+    assert x.dim() == 2
+    return _DropoutRows.apply(x, p, seed, layer, seed_dev, row_bound)
+
+
+class _MolnetHead(torch.autograd.Function):
+    """global_mean_pool + graph_pred_linear of finetune_MoleculeNet.py:120-124 (msde_molnet_head_fwd / _bwd).  The weight and
+    bias gradients are ordinary weight gradients (queued into the step's grouped launch when a batch is open)."""
+
+    @staticmethod
+    def forward(ctx, h, W, b, mol_ptr, row_bound):
+        h, W = _f32(h), _f32(W)
+        b = _f32(b) if b is not None else None
+        M, D = h.shape
+        T = W.size(0)
+        B = mol_ptr.numel() - 1
+        assert W.size(1) == D
+        pool = torch.empty(B, D, dtype=torch.float32, device=h.device)
+        logits = torch.empty(B, T, dtype=torch.float32, device=h.device)
+        _lib.call("msde_molnet_head_fwd", _p(h), D, M, D, _p(mol_ptr), B, _p(row_bound), _p(W), _p(b), T, _p(pool),
+                  _p(logits), _stream())
+        ctx.save_for_backward(pool, W)
+        ctx.cfg = (M, mol_ptr, row_bound, b is not None)
+        ctx.deferrable = W.is_leaf and (b is None or b.is_leaf)
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        pool, W = ctx.saved_tensors
+        M, mol_ptr, row_bound, has_bias = ctx.cfg
+        g = _f32(g)
+        B, T = g.shape
+        D = W.size(1)
+        dh = torch.empty(M, D, dtype=torch.float32, device=g.device)
+        _lib.call("msde_molnet_head_bwd", _p(g), B, T, _p(W), D, _p(mol_ptr), _p(row_bound), M, _p(dh), D, _stream())
+        gW, gb = weight_grad(g, pool, has_bias, ctx.deferrable)
+        return dh, gW, gb, None, None
+
+
+def molnet_head(h, W, b, mol_ptr, row_bound=None):
+    """logits [B, T] = global_mean_pool(h, batch) W^T + b for the ragged layout mol_ptr (int32 [B + 1]); the pooled rows are
+    kept for the backward.  row_bound: device int32 scalar with the true row count of h (None: all rows)."""
+    return _MolnetHead.apply(h, W, b, _i32(mol_ptr), row_bound)
+
+
+def molnet_bce(logits, y, want_loss_mat=False, want_grad=True):
+    """The masked multi-task BCEWithLogitsLoss of finetune_MoleculeNet.py:127-141 in fp64, one launch.  y [B, T] in
+    {-1, 0, +1}.  Returns (stats, dlogits, loss_mat): stats = fp64 device [loss, valid count, NaN logits], dlogits = d loss
+    / d logits (fp32, None unless want_grad), loss_mat fp64 [B, T] (None unless want_loss_mat)."""
+    logits, y = _f32(logits), _f32(y)
+    B, T = logits.shape
+    assert y.shape == logits.shape
+    stats = torch.empty(3, dtype=torch.float64, device=logits.device)
+    dl = torch.empty_like(logits) if want_grad else None
+    lm = torch.empty(B, T, dtype=torch.float64, device=logits.device) if want_loss_mat else None
+    _lib.call("msde_molnet_bce", _p(logits), _p(y), B, T, _p(lm), _p(stats), _p(dl), _stream())
+    return stats, dl, lm
+
+
 class _MulAdd(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, c):

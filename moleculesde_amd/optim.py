@@ -87,6 +87,14 @@ class FlatAdam:
                              torch.tensor([seg_lr[i]], dtype=torch.float32, device=dev))
                             for i, (a, b) in enumerate(self.bucket_ranges)]
 
+    def set_lr(self, lrs):
+        """New learning rate of every param group (a scheduler step): written into the device tables the kernels read."""
+        lrs = [float(v) for v in lrs]
+        assert len(lrs) == len(self._bucket_seg)
+        self.seg_lr.copy_(torch.tensor(lrs, dtype=torch.float32))
+        for (_, lr_t), v in zip(self._bucket_seg, lrs):
+            lr_t.fill_(v)
+
     def zero_grad(self):
         for p in self.params:
             p.grad = None

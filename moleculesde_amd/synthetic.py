@@ -97,6 +97,34 @@ def make_md17_batch(num_graphs=1, seed=0, n_atoms=21):
     return Batch.from_data_list(mols)
 
 
+def molnet_sizes(rng, num_graphs, max_atoms=150, tail=0.03):
+    """Heavy-atom counts of a MoleculeNet-shaped batch: round(lognormal(log 22, 0.4)) clipped to [2, 60] for most molecules,
+    a `tail` fraction uniform in [60, max_atoms].  UNVERIFIED: no MoleculeNet dataset exists here; the shape follows figures
+    quoted from memory (Tox21 averages about 18 heavy atoms, HIV has molecules past 200) and is meant to put molecules of
+    more than 32 atoms into every batch, not to match any dataset's histogram."""
+    n = np.clip(np.rint(rng.lognormal(np.log(22.0), 0.4, size=num_graphs)), 2, 60).astype(np.int64)
+    big = rng.random(num_graphs) < tail
+    n[big] = rng.integers(60, max_atoms + 1, size=int(big.sum()))
+    return n
+
+
+def make_molnet_batch(num_graphs=32, num_tasks=12, seed=0, missing=0.2, pos_rate=0.2, max_atoms=150, tail=0.03, sizes=None):
+    """MoleculeNet-shaped 2D batch (finetune_MoleculeNet.py): x [N, 9], edge_index, edge_attr [E, 3] and labels y [B, T] in
+    {-1, 0, +1} (float32, 0 = missing with probability `missing`, +1 with probability `pos_rate` among the rest).  Sizes from
+    molnet_sizes (or `sizes`).  No positions: the fine-tune reads the 2D graph only."""
+    rng = np.random.default_rng(seed)
+    sizes = molnet_sizes(rng, num_graphs, max_atoms, tail) if sizes is None else np.asarray(sizes, dtype=np.int64)
+    mols = []
+    for i in range(num_graphs):
+        m = make_molecule(rng, int(sizes[i]))
+        del m.positions, m.extended_edge_index
+        lab = np.where(rng.random(num_tasks) < pos_rate, 1.0, -1.0)
+        lab[rng.random(num_tasks) < missing] = 0.0
+        m.y = torch.from_numpy(lab.astype(np.float32)).view(1, num_tasks)
+        mols.append(m)
+    return Batch.from_data_list(mols)
+
+
 def batch_stats(b, cutoff=10.0):
     """N, E_b, E_e, E_r (radius edges, strict < cutoff, no self loops), sum n^2, N_max."""
     N = b.x.size(0)
