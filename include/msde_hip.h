@@ -946,6 +946,23 @@ int msde_molnet_bce(const float* logits, const float* y, int B, int T, double* l
 int msde_molnet_head_bwd(const float* dlogits, int B, int T, const float* W, int D, const int* mol_ptr,
                          const int* row_bound, int M, float* dh, int ldh, void* stream);
 
+/* ------------------------------------------------------------------ QM9 head --------------- */
+/* examples/finetune_QM9.py:145-171 and :185-223: graph_pred_linear = Linear(D, 1) on the readout out [B, D] (row stride ldo),
+ * raw targets y[m * ldy], standardised in fp32 as (y - mean) / std.  One workgroup, B <= 8192, D <= 1024; fixed-order fp64
+ * sums without atomics: bitwise repeatable.
+ *   msde_qm9_head_train: pred [B] (may be NULL), loss[0] = mean |pred - yhat| (mode 0, L1) or mean (pred - yhat)^2 (mode 1,
+ *     MSE) (may be NULL), loss_acc[0] += loss (fp64, may be NULL), and the head's backward in the same launch: dpred =
+ *     sign(pred - yhat) / B (sign(0) = 0) or 2 (pred - yhat) / B, dout [B, D] = dpred W (row stride D), dW [D] =
+ *     sum_m dpred_m out_m, db[0] = sum_m dpred_m.  Loss-only form: W == NULL, b, dW and db NULL; out[m * ldo] is the
+ *     prediction and dout [B] receives dpred.
+ *   msde_qm9_head_eval: pred [B] = (out W^T + b) * std + mean (W == NULL: out[m * ldo] * std + mean) (may be NULL), and
+ *     acc[0] += sum_m |pred_m - y_m|, acc[1] += B (fp64; acc may be NULL, y may be NULL when acc is). */
+int msde_qm9_head_train(const float* out, int ldo, int B, int D, const float* W, const float* b, const float* y, int ldy,
+                        float mean, float std, int mode, float* pred, float* loss, float* dout, float* dW, float* db,
+                        double* loss_acc, void* stream);
+int msde_qm9_head_eval(const float* out, int ldo, int B, int D, const float* W, const float* b, const float* y, int ldy,
+                       float mean, float std, float* pred, double* acc, void* stream);
+
 /* ------------------------------------------------------------------ optimiser -------------- */
 /* torch.optim.Adam step over a flat parameter buffer with per-element lr via segment table —
  * examples/pretrain_MoleculeSDE.py:331-337,156.  seg_end[S] (exclusive ends), seg_lr[S].

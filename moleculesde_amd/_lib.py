@@ -148,6 +148,8 @@ SIGNATURES = {
     "msde_molnet_head_fwd": [P, I, I, I, P, I, P, P, P, I, P, P, P],
     "msde_molnet_bce": [P, P, I, I, P, P, P, P],
     "msde_molnet_head_bwd": [P, I, I, P, I, P, P, I, P, I, P],
+    "msde_qm9_head_train": [P, I, I, I, P, P, P, I, F, F, I, P, P, P, P, P, P, P],
+    "msde_qm9_head_eval": [P, I, I, I, P, P, P, I, F, F, P, P, P],
     "msde_mul_add_fwd": [P, P, P, LL, P, P],
     "msde_mul_add_bwd": [P, P, P, LL, P, P, P],
     "msde_pc_corrector": [P, P, P, P, P, ULL, I, F, F, P, P, P],

@@ -73,11 +73,15 @@ class Caps:
 
 
 # ------------------------------------------------------------------------------------------------ raw batches
-def raw_layout(caps):
-    """Offsets (in int32 words) of the fields of the raw blob."""
+def raw_layout(caps, k=K_ATOM, targets=False):
+    """Offsets (in int32 words) of the fields of the raw blob.  k: atom feature columns (1 for a 1-D atomic number);
+    targets: one fp32 target per molecule (field "y") after the other fields."""
     o, lay = 0, {}
-    for name, n in (("x", caps.N * K_ATOM), ("pos", caps.N * 3), ("bond_src", caps.E_b), ("bond_dst", caps.E_b),
-                    ("bond_attr", caps.E_b * 3), ("mol_atoms", caps.B), ("mol_bonds", caps.B)):
+    fields = (("x", caps.N * k), ("pos", caps.N * 3), ("bond_src", caps.E_b), ("bond_dst", caps.E_b),
+              ("bond_attr", caps.E_b * 3), ("mol_atoms", caps.B), ("mol_bonds", caps.B))
+    if targets:
+        fields += (("y", caps.B),)
+    for name, n in fields:
         lay[name] = (o, n)
         o += (n + 3) & ~3
     lay["_total"] = o
@@ -126,18 +130,58 @@ def pack_raw(b, caps, pin=False):
     return blob
 
 
+# ------------------------------------------------------------------------------------------------ 1-D z batches
+def raw_sizes_z(b):
+    """raw_sizes of a batch with a 1-D atomic number `x` whose bonds the blob does not carry (QM9 property regression: the
+    encoder reads z, positions and the molecule index only): no bonds, hence no extended edges."""
+    n = torch.bincount(b.batch, minlength=b.num_graphs).numpy().astype(np.int64)
+    return {"B": int(b.num_graphs), "N": int(b.x.size(0)), "E_b": 0, "E_e": 0,
+            "E_r": int((n * np.minimum(np.maximum(n - 1, 0), MAX_NBR)).sum()), "P": int((n * n).sum()),
+            "n_max": int(n.max()) if len(n) else 0}
+
+
+def pack_raw_z(b, caps, y, pin=False):
+    """Raw blob (int32, host) of a collated 1-D z batch with one fp32 target per molecule `y` [B] for a bucket made with
+    z_only=True: x as [N, 1], positions, atoms per molecule, no bonds, the targets last (raw_layout(caps, 1, True))."""
+    need = raw_sizes_z(b)
+    if not caps.fits(need) or need["n_max"] > PLAN_NMAX:
+        raise BucketOverflow(f"batch {need} does not fit the bucket {caps.as_dict()}")
+    assert b.x.dim() == 1
+    y = torch.as_tensor(y).reshape(-1)
+    assert y.numel() == b.num_graphs
+    lay = raw_layout(caps, 1, True)
+    blob = torch.zeros(lay["_total"], dtype=torch.int32)
+    if pin:
+        blob = blob.pin_memory()
+    N = b.x.size(0)
+    o, _ = lay["x"]
+    blob[o:o + N] = b.x.to(torch.int32)
+    o, _ = lay["pos"]
+    blob[o:o + 3 * N] = b.positions.float().contiguous().view(-1).view(torch.int32)
+    o, _ = lay["mol_atoms"]
+    blob[o:o + b.num_graphs] = torch.bincount(b.batch, minlength=b.num_graphs).to(torch.int32)
+    o, _ = lay["y"]
+    blob[o:o + b.num_graphs] = y.float().contiguous().view(torch.int32)
+    return blob
+
+
 # ------------------------------------------------------------------------------------------------ the bucket
 class Bucket:
-    def __init__(self, caps, device, atom_dims=None, bond_dims=None, node_class=119):
+    def __init__(self, caps, device, atom_dims=None, bond_dims=None, node_class=119, z_only=False):
+        """z_only: batches with a 1-D atomic number and one target per molecule (pack_raw_z); the plan then holds the
+        atomic-number lists only, and `batch.x` is a 1-D int64 placeholder."""
         self.caps, self.device = caps, device
-        atom_dims = list(atom_dims or _plan.ATOM_FEATURE_DIMS)
+        self.z_only = bool(z_only)
+        self.k = 1 if z_only else K_ATOM
+        atom_dims = list(atom_dims or ([node_class] if z_only else _plan.ATOM_FEATURE_DIMS))
         bond_dims = list(bond_dims or _plan.BOND_FEATURE_DIMS)
         c = caps
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
-        self.layout = raw_layout(c)
+        self.layout = raw_layout(c, self.k, z_only)
         self.raw = i32(self.layout["_total"])
         v = lambda name: self.raw[self.layout[name][0]:self.layout[name][0] + self.layout[name][1]]
-        self.x_raw = v("x").view(c.N, K_ATOM)
+        self.x_raw = v("x").view(c.N, self.k)
+        self.y = v("y").view(torch.float32) if z_only else None
         self.positions = v("pos").view(torch.float32).view(c.N, 3)
         self.bond_src_raw, self.bond_dst_raw, self.bond_attr_raw = v("bond_src"), v("bond_dst"), v("bond_attr").view(c.E_b, 3)
         self.mol_atoms, self.mol_bonds = v("mol_atoms"), v("mol_bonds")
@@ -151,9 +195,9 @@ class Bucket:
         pl.err_dev = self.err             # kernels that can detect a capacity overflow of their own raise the bucket's flag
         pl.mol_ptr = self.mol_ptr_full[:c.B + 1]
         pl.batch_i32 = i32(c.N)
-        pl.atom_codes, pl.atom_R = i32(c.N, K_ATOM), sum(atom_dims)
+        pl.atom_codes, pl.atom_R = i32(c.N, self.k), sum(atom_dims)
         pl.z_codes, pl.z_list = i32(c.N, 1), None
-        pl.atom_list_ptr, pl.atom_list_nodes = i32(pl.atom_R + 1), i32(c.N * K_ATOM)
+        pl.atom_list_ptr, pl.atom_list_nodes = i32(pl.atom_R + 1), i32(c.N * self.k)
         self._cnt_scratch = i32(max(pl.atom_R, node_class) + 1)
         self.node_class = node_class
         pl.z_list = (node_class, i32(node_class + 1), i32(c.N))
@@ -175,7 +219,7 @@ class Bucket:
         # the Batch-like object the models see: tensors whose VALUES the kernels never read (identity / dtype only) are
         # static placeholders; coordinates are the live view of the raw blob
         z64 = lambda *s: torch.zeros(*s, dtype=torch.int64, device=device)
-        b = Batch(x=z64(c.N, K_ATOM), edge_index=z64(2, c.E_b), edge_attr=z64(c.E_b, 3), positions=self.positions,
+        b = Batch(x=z64(c.N) if z_only else z64(c.N, K_ATOM), edge_index=z64(2, c.E_b), edge_attr=z64(c.E_b, 3), positions=self.positions,
                   extended_edge_index=z64(2, 8), batch=z64(c.N))
         b.num_graphs = c.B
         b._msde_plan = pl
@@ -195,7 +239,7 @@ class Bucket:
         there, behind the CSR build, so the forward of the main chain starts without them; the caller's streams must be
         joined before the backward pass (the trainer's second stream is)."""
         c, pl, p, st = self.caps, self.plan, hip._p, hip._stream()
-        _lib.call("msde_plan_build", p(self.x_raw), K_ATOM, p(self.atom_off), p(self.bond_src_raw), p(self.bond_dst_raw),
+        _lib.call("msde_plan_build", p(self.x_raw), self.k, p(self.atom_off), p(self.bond_src_raw), p(self.bond_dst_raw),
                   p(self.bond_attr_raw), p(self.bond_off), p(self.mol_atoms), p(self.mol_bonds), c.B, c.N, c.E_b, c.E_e,
                   c.P, c.E_r, MAX_NBR, p(self.mol_ptr_full), p(self.bond_ptr), p(self.pair_ptr), p(self.sizes), p(pl.batch_i32),
                   p(pl.atom_codes), p(pl.z_codes), p(pl.bond.rowptr), p(pl.bond.src), p(pl.bond.dst), p(pl.bond.rowptr_s),
@@ -203,8 +247,9 @@ class Bucket:
                   p(pl.ext.rowptr), p(pl.ext.src), p(pl.ext.dst), p(pl.ext.rowptr_s), p(pl.ext.perm_s), p(self.err), st)
         # (msde_plan_build clears *err itself at the start of every build)
         def lists(st_):
-            _lib.call("msde_plan_row_lists", p(pl.atom_codes), p(pl.N_dev), K_ATOM, pl.atom_R, p(self._cnt_scratch),
-                      p(pl.atom_list_ptr), p(pl.atom_list_nodes), st_)
+            if not self.z_only:       # (the atom-feature lists feed the GIN embedding backward only)
+                _lib.call("msde_plan_row_lists", p(pl.atom_codes), p(pl.N_dev), K_ATOM, pl.atom_R, p(self._cnt_scratch),
+                          p(pl.atom_list_ptr), p(pl.atom_list_nodes), st_)
             _lib.call("msde_plan_row_lists", p(pl.z_codes), p(pl.N_dev), 1, self.node_class, p(self._cnt_scratch),
                       p(pl.z_list[1]), p(pl.z_list[2]), st_)
         if side_stream is None:

@@ -1715,6 +1715,49 @@ def molnet_bce(logits, y, want_loss_mat=False, want_grad=True):
     return stats, dl, lm
 
 
+QM9_LOSS_MODES = {"mae": 0, "mse": 1}
+
+
+def qm9_head_train(out, W, b, y, mean, std, loss="mae", dW=None, db=None, loss_acc=None, pred=None, loss_out=None):
+    """graph_pred_linear + the standardised L1 / MSE loss of finetune_QM9.py:145-171 and the head's backward, one launch
+    (msde_qm9_head_train).  out [B, D] (the readout; W [1, D], b [1]) or, with W None, the predictions [B] themselves (the
+    loss-only form).  y: raw targets [B] or a strided column view.  dW [D] / db [1] (the head's .grad buffers) are written
+    in place; loss_acc (fp64 [1]) gets the loss added.  Returns (pred [B], loss [1] fp32, dout: [B, D] with W, [B] without)."""
+    out = _f32(out)
+    B = out.size(0)
+    assert y.dim() == 1 and y.numel() == B and y.dtype == torch.float32
+    if W is not None:
+        assert out.dim() == 2 and out.stride(1) == 1
+        D = out.size(1)
+        W = _f32(W)
+        assert W.numel() == D and b is not None and b.numel() == 1 and dW is not None and db is not None
+        dout = torch.empty(B, D, dtype=torch.float32, device=out.device)
+        ldo = out.stride(0)
+    else:
+        assert out.dim() == 1 or (out.dim() == 2 and out.size(1) == 1)
+        D, ldo = 1, out.stride(0)
+        dout = torch.empty(B, dtype=torch.float32, device=out.device)
+    pred = torch.empty(B, dtype=torch.float32, device=out.device) if pred is None else pred
+    loss_out = torch.empty(1, dtype=torch.float32, device=out.device) if loss_out is None else loss_out
+    _lib.call("msde_qm9_head_train", _p(out), ldo, B, D, _p(W), _p(b), _p(y), y.stride(0), float(mean), float(std),
+              QM9_LOSS_MODES[loss], _p(pred), _p(loss_out), _p(dout), _p(dW), _p(db), _p(loss_acc), _stream())
+    return pred, loss_out, dout
+
+
+def qm9_head_eval(out, W, b, y, mean, std, acc, pred=None):
+    """Evaluation form (msde_qm9_head_eval): pred [B] = (out W^T + b) * std + mean (W None: out * std + mean), and
+    acc[0] += sum |pred - y|, acc[1] += B in fp64 on the device (y None: predictions only)."""
+    out = _f32(out)
+    B = out.size(0)
+    D = out.size(1) if W is not None else 1
+    pred = torch.empty(B, dtype=torch.float32, device=out.device) if pred is None else pred
+    if y is not None:
+        assert y.dim() == 1 and y.numel() == B and y.dtype == torch.float32
+    _lib.call("msde_qm9_head_eval", _p(out), out.stride(0), B, D, _p(None if W is None else _f32(W)), _p(b), _p(y),
+              1 if y is None else y.stride(0), float(mean), float(std), _p(pred), _p(acc if y is not None else None), _stream())
+    return pred
+
+
 class _MulAdd(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, c):

@@ -86,6 +86,43 @@ def make_qm9_batch(num_graphs=32, seed=0):
     return Batch.from_data_list(mols)
 
 
+def make_qm9_targets(b, seed=0, noise=0.05):
+    """Targets [B, 13] (float32) of a 1-D z batch as a deterministic function of the molecule: per target, a sum of per-
+    element contributions, a term in the mean interatomic distance, and seeded noise -- something a property regression can
+    actually fit.  The coefficients are fixed (seed 1234); `seed` draws the noise only."""
+    coef = np.random.default_rng(1234)
+    per_z = coef.normal(0.0, 1.0, size=(119, 13))
+    per_r = coef.normal(0.0, 1.0, size=13)
+    rng = np.random.default_rng(seed)
+    z = b.x.numpy() if b.x.dim() == 1 else b.x[:, 0].numpy()
+    pos = b.positions.detach().double().numpy()
+    cnt = torch.bincount(b.batch, minlength=b.num_graphs).numpy()
+    out = np.zeros((b.num_graphs, 13))
+    a = 0
+    for i, n in enumerate(cnt):
+        zz, p = z[a:a + n], pos[a:a + n]
+        d = np.sqrt(((p[:, None] - p[None]) ** 2).sum(-1))
+        r = d.sum() / max(n * (n - 1), 1)
+        out[i] = per_z[zz].sum(0) / np.sqrt(max(n, 1)) + per_r * r
+        a += n
+    out += noise * rng.normal(size=out.shape)
+    return torch.from_numpy(out.astype(np.float32))
+
+
+def seeded_parameters(module, seed=0):
+    """Overwrite every parameter of `module` with a seeded draw that depends on its NAME and shape only (crc32 of the name
+    folded into the seed; normal / sqrt(fan_in) for matrices, 0.1 * normal for vectors): two modules with the same parameter
+    names get the same values whatever their construction order, so a stored fixture need not carry initial weights."""
+    import zlib
+    with torch.no_grad():
+        for name, p in module.named_parameters():
+            g = torch.Generator().manual_seed((int(seed) * 1000003 + zlib.crc32(name.encode())) & 0x7FFFFFFFFFFFFFFF)
+            v = torch.randn(p.shape, generator=g, dtype=torch.float32)
+            v = v / float(np.sqrt(p.shape[-1])) if p.dim() >= 2 else 0.1 * v
+            p.copy_(v.to(p.device, p.dtype))
+    return module
+
+
 def make_md17_batch(num_graphs=1, seed=0, n_atoms=21):
     """MD17-aspirin-shaped batch (config 5): 21 atoms, 1-D z."""
     rng = np.random.default_rng(seed)
