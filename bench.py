@@ -2,22 +2,26 @@
 
     python bench.py --gpus 1 --steps 20 --warmup 5
     python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR     # + DIR/*.npy: the last timed step's results
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                 # + every secondary measurement (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 Workload (BASELINE.json configs[1]): PCQM4Mv2-shaped synthetic batches, 256 molecules per GPU,
 GIN(5x300) + SchNet(6 interactions, 128 filters, 51 Gaussians, cutoff 10) + contrastive
 (EBM_node_dot_prod, so SchNet receives gradient) + SDEModel2Dto3D_02 VE; one "step" = device-side batch
-construction, forward, backward, (all-reduce), Adam, inputs already resident in HBM.  `--full` adds the 3D->2D dense
-head (configs[2] per-GPU work).  Weak scaling: every rank owns its own shard of molecules; the only collective is the
-all-reduce of the flat gradient (per-model buckets).
+construction, forward, backward, (all-reduce), Adam, inputs already resident in HBM.  `--config2` adds the 3D->2D dense
+head (configs[2] per-GPU work) to the headline's step.  Weak scaling: every rank owns its own shard of molecules; the only
+collective is the all-reduce of the flat gradient (per-model buckets).
 
 Headline (`value`): `--stream` (64) DISTINCT batches streamed through ONE captured hipGraph (capacity bucket, raw
-collated arrays in, plans + extended graph built on the device).  Secondary keys under config.stream: the same blobs
-from pinned host memory (PCIe-inclusive) and the round-1 mode (4 resident batches, a graph each).
+collated arrays in, plans + extended graph built on the device).  A plain run does only what the headline needs: set-up,
+warm-up, the trainer's steps in front of the headline's timed loop (they make the state its outputs are dumped from), the
+timed steps, `--dump-outputs`, the line.  Everything else is measured under `--full` alone: under config.stream the same
+blobs from pinned host memory (PCIe-inclusive) and the two-bucket mode; `config2_full` (configs[2] timed behind the
+headline); the DP step pieces; the keys below.
 
-Rank 0 prints ONE JSON line; `roofline` = the kernel with the largest share of the step's GPU time (round 3: the row-strip
-fp32-MFMA GEMM on the GIN layer's 3588 x 300 x 600 product), its duration measured INSIDE the captured step with device
+Rank 0 prints ONE JSON line.  Under `--full`: `roofline` = the kernel with the largest share of the step's GPU time
+(round 3: the row-strip fp32-MFMA GEMM on the GIN layer's 3588 x 300 x 600 product), its duration measured INSIDE the captured step with device
 timestamps (both streams running), the stand-alone HIP-event timing kept under `standalone`;
 `roofline_forward_schnet_sde2d3d` = the north-star forward figure; `config4_sampler` / `config5_md17` = BASELINE.json
 configs[3] / configs[4] with the oracle's CPU time beside them; `cpu_baseline` = the oracle port of the pretrain step timed on
@@ -779,7 +783,7 @@ def cpu_baseline(bs=256):
 
 # Keys every `--gpus N` line carries beside the contract's own (tests/test_host_logic.py asserts them on the launcher path,
 # tools/dp2_gloo_smoke.sh on a real step): configs[2]'s full step timed by the same ranks, the pieces of a DP step, the
-# per-rank spread.
+# per-rank spread.  The first two are measured under --full only and are None on a plain line.
 DUMP_BUDGET_BYTES = 64 * 10**6    # --dump-outputs: all arrays together
 
 
@@ -951,8 +955,12 @@ def main():
     ap.add_argument("--debug_dp_path", action="store_true",
                     help="one GPU: initialise a 1-rank RCCL group and run the multi-GPU step structure "
                          "(graph without Adam; all-reduce; Adam kernel)")
+    ap.add_argument("--config2", action="store_true",
+                    help="configs[2] per-GPU work: add the 3D->2D dense head loss to the headline's step (default: configs[1])")
     ap.add_argument("--full", action="store_true",
-                    help="configs[2] per-GPU work: add the 3D->2D dense head loss (default: configs[1])")
+                    help="every secondary measurement beside the headline: the other stream modes, configs[2] timed behind "
+                         "it, the DP step pieces, in-step and stand-alone kernel timings, rooflines, configs[3] / configs[4] "
+                         "and the CPU baseline (the --no_* options leave parts out); a plain run times the headline alone")
     ap.add_argument("--score_kernel", default="ops", choices=["ops", "mol"],
                     help="2D->3D score network under autograd: operator by operator (default) or one launch each way with one "
                          "workgroup per molecule (pretrain.py --score_kernel)")
@@ -1007,7 +1015,7 @@ def main():
     torch.cuda.set_device(device)
     torch.manual_seed(0)
 
-    args = pretrain.readme_args(SDE_coeff_generative_3Dto2D=1 if a.full else 0, batch_size=a.batch_size, score_kernel=a.score_kernel)
+    args = pretrain.readme_args(SDE_coeff_generative_3Dto2D=1 if a.config2 else 0, batch_size=a.batch_size, score_kernel=a.score_kernel)
     trainer = pretrain.Trainer(args, device)
     trainer.adam_outside_graph = a.debug_dp_path
     cpu_pool = [make_batch(a.batch_size, seed=dp.shard_seed(s, rank)) for s in range(a.pool)]
@@ -1074,13 +1082,13 @@ def main():
     dt, launch, stream_info = dt_pool, None, None
     dt_local = local_s.get("last", dt_pool)
 
-    def stream_modes(tr, full, pcie_variants=True, headline=True):
+    def stream_modes(tr, config2, pcie_variants=True, headline=True):
         """`--stream` DISTINCT batches, each fed as its raw collated arrays (one device-to-device copy of the resident blob),
         plans and the extended graph built on the device inside the ONE captured graph of trainer `tr`; then the two-bucket
         mode and (pcie_variants) the blobs from pinned host memory.  Which mode is the headline is a FIXED rule, not "the
         faster one": configs[1] -> the one-graph mode, the full step (configs[2]'s per-GPU work) -> the two-bucket mode; both
-        times are reported either way.  Returns (seconds of the headline mode, this rank's own seconds, launch text, info,
-        (bucket, blobs))."""
+        times are reported under --full, a plain run stops at the headline's.  Returns (seconds of the headline mode, this
+        rank's own seconds, launch text, info, (bucket, blobs))."""
         from moleculesde_amd import bucket as BK
         t0 = time.perf_counter()
         extra = [make_batch(a.batch_size, seed=dp.shard_seed(1000 + s, rank)) for s in range(max(a.stream - len(cpu_pool), 0))]
@@ -1097,14 +1105,14 @@ def main():
         assert ok
         dt_ = timed(lambda blob: tr.step_bucket(bk, blob), blobs, a.steps)
         dtl_ = local_s["last"]
-        if headline and (not full or a.no_pipeline):
+        if headline and (not config2 or a.no_pipeline):
             snap("stream", tr)
         ok, _ = bk.check()
         assert ok
         launch_ = ("ONE hipGraph for all batches: %d distinct batches streamed as raw collated arrays (1 copy each), "
                    "plans + extend_graph built on the device inside the graph" % len(blobs))
         dt_one_graph, dt_pipe = dt_, None
-        if not a.no_pipeline:
+        if not a.no_pipeline and (a.full or config2):
             # two buckets used alternately: the plans of batch t+1 are built (plan graph, third stream) while the
             # step of batch t runs -- the same work per batch, batch construction off the step's critical path
             pipe = pretrain.BucketPipeline(tr, caps, blobs[0])
@@ -1119,12 +1127,12 @@ def main():
                 piped_step(None)
             dt_pipe = timed(piped_step, blobs, a.steps)
             dtl_pipe = local_s["last"]
-            if headline and full:
+            if headline and config2:
                 snap("stream", tr)
             pipe.step()                       # drain the batch submitted last
             torch.cuda.synchronize()
             assert pipe.check()
-            if full:
+            if config2:
                 dt_, dtl_ = dt_pipe, dtl_pipe
                 launch_ = ("two capacity buckets used alternately (one captured step graph + one plan graph each): %d "
                            "distinct batches streamed as raw collated arrays (1 copy each); plans + extend_graph of "
@@ -1137,7 +1145,7 @@ def main():
                 "ms_per_step_one_graph_plan_inside": round(dt_one_graph / a.steps * 1e3, 3),
                 "ms_per_step_two_buckets_plan_ahead": None if dt_pipe is None else round(dt_pipe / a.steps * 1e3, 3),
                 "host_prep_s_synthetic_generation_and_packing": round(host_prep_s, 2)}
-        if pcie_variants:
+        if pcie_variants and a.full:
             # PCIe-inclusive variant: the same blobs from pinned host memory
             pinned = [BK.pack_raw(b, caps, pin=True) for b in stream_cpu[:16]]
             dt_h2d = timed(lambda blob: tr.step_bucket(bk, blob), pinned, a.steps)
@@ -1159,9 +1167,9 @@ def main():
     dp_parts = None
     if a.stream > 0 and use_graph:
         try:
-            dt, dt_local, launch, stream_info, (bk0, blobs0) = stream_modes(trainer, a.full)
+            dt, dt_local, launch, stream_info, (bk0, blobs0) = stream_modes(trainer, a.config2)
             stream_info["ms_per_step_4_resident_batches_own_graphs"] = round(dt_pool / a.steps * 1e3, 3)
-            if trainer._use_dp():
+            if a.full and trainer._use_dp():
                 dp_parts = dp_step_parts(trainer, lambda i: trainer.step_bucket(bk0, blobs0[i % len(blobs0)]))
         except Exception as exc:
             print(f"[bench] bucket mode failed ({type(exc).__name__}: {exc}); reporting the per-shape-graph mode",
@@ -1171,15 +1179,15 @@ def main():
         finally:
             from moleculesde_amd import hip as _hip
             _hip.clear_row_bounds()
-    if dp_parts is None and trainer._use_dp() and use_graph:
+    if a.full and dp_parts is None and trainer._use_dp() and use_graph:
         dp_parts = dp_step_parts(trainer, lambda i: trainer.step_graph(pool[i % len(pool)]))
 
     # configs[2] (BASELINE.json: contrastive + 2D->3D + 3D->2D, 256 molecules per GPU, DP): the SAME ranks time the full step on
-    # a second Trainer right behind the headline, so that one `--gpus N` run measures both configurations
+    # a second Trainer right behind the headline, so that one `--gpus N --full` run measures both configurations
     # (examples/pretrain_MoleculeSDE.py:135-156 is the loss composition the full step adds to).  Every rank takes part:
     # the trainer's collectives and timed()'s barriers need all of them.
     config2 = None
-    if not a.full and not a.no_config2 and a.stream > 0 and use_graph:
+    if a.full and not a.config2 and not a.no_config2 and a.stream > 0 and use_graph:
         try:
             args2 = pretrain.readme_args(SDE_coeff_generative_3Dto2D=1, batch_size=a.batch_size, score_kernel=a.score_kernel)
             tr2 = pretrain.Trainer(args2, device)
@@ -1236,21 +1244,44 @@ def main():
     if rank == 0:
         print(f"[bench] {a.steps} steps in {dt:.3f}s", file=sys.stderr, flush=True)
         mols = world * a.batch_size * a.steps
-        # everything below is measured by rank 0 ALONE while the other ranks wait at the final barrier: the trainer must not
-        # issue collectives any more (found by the 2-rank smoke run: the kernel count's eager step hung in its all-reduce)
-        trainer.dp_enabled = False
-        # `roofline` = the kernel with the largest share of the step's GPU time (profiles/*_kernel_stats.csv):
-        # cfconv_fused_bwd_w, timed at the workgroup count the step launches it with; the full-width figures are
-        # kept as separate keys
-        roof_filter = roofline_pair_filter(trainer, pool[0])
-        roof_bwd = roofline_pair_bwd_w(trainer, pool[0])
-        in_step = in_step_stamps(trainer, cpu_pool[0].clone(), device)
-        roof_agg = roofline_hbm_kernel(trainer, pool[0], in_step)
-        family = in_step_family(trainer, cpu_pool[0].clone(), device)
-        roof = roofline_gemm(trainer, cpu_pool[0].clone(), device, in_step, family)
-        n_kern, n_foreign = count_kernels_per_step(trainer, pool[0])
-        roof_head = roofline_dense_head_node_mlp(pool[0])
-        roof_forward = roofline_forward(trainer, pool[0], stats)
+        extra = {}
+        if a.full:
+            # everything below is measured by rank 0 ALONE while the other ranks wait at the final barrier: the trainer must
+            # not issue collectives any more (found by the 2-rank smoke run: the kernel count's eager step hung in its all-reduce)
+            trainer.dp_enabled = False
+            # `roofline` = the kernel with the largest share of the step's GPU time (profiles/*_kernel_stats.csv):
+            # cfconv_fused_bwd_w, timed at the workgroup count the step launches it with; the full-width figures are
+            # kept as separate keys
+            roof_filter = roofline_pair_filter(trainer, pool[0])
+            roof_bwd = roofline_pair_bwd_w(trainer, pool[0])
+            in_step = in_step_stamps(trainer, cpu_pool[0].clone(), device)
+            roof_agg = roofline_hbm_kernel(trainer, pool[0], in_step)
+            family = in_step_family(trainer, cpu_pool[0].clone(), device)
+            roof = roofline_gemm(trainer, cpu_pool[0].clone(), device, in_step, family)
+            n_kern, n_foreign = count_kernels_per_step(trainer, pool[0])
+            roof_head = roofline_dense_head_node_mlp(pool[0])
+            roof_forward = roofline_forward(trainer, pool[0], stats)
+            extra = {
+                "tail_us": None if in_step.get("tail") is None else round(in_step["tail"], 1),
+                "tail_us_what": "end of the backward chain of the main stream -> end of Adam and of the weight-copy refresh, "
+                                "device stamps inside the captured per-shape step (grouped weight gradients, slab reduction, Adam)",
+                "tail_after_both_streams_us": None if in_step.get("tail_both") is None else round(in_step["tail_both"], 1),
+                "tail_after_both_streams_what": "end of the SECOND stream's work of the backward pass INCLUDING its deferred leaf "
+                                                "kernels (embedding / bond-table gradients, which run beside the grouped "
+                                                "weight-gradient launch) -> end of Adam and of the weight-copy refresh",
+                "tail_after_side_chain_us": None if in_step.get("tail_chain") is None else round(in_step["tail_chain"], 1),
+                "tail_after_side_chain_what": "end of the second stream's backward CHAIN (SchNet's backward, before its leaf "
+                                              "kernels) -> end of the step: with tail_us, how serial the grouped launch + "
+                                              "reduction + Adam are",
+                "step_us_device_stamps": None if in_step.get("step") is None else round(in_step["step"], 1),
+                "kernels_per_step": n_kern, "kernels_per_step_not_from_libmsde_hip": n_foreign,
+                "roofline": roof,
+                "roofline_cfconv_pair_filter": roof_filter,
+                "roofline_cfconv_pair_bwd_w": roof_bwd,
+                "roofline_hbm_message_passing": roof_agg,
+                "roofline_forward_schnet_sde2d3d": roof_forward,
+                "roofline_dense_head_node_mlp": roof_head,
+            }
         out = {
             "metric": "molecules/sec pretrain step (SchNet+SDE VE, bs256)",
             "value": round(mols / dt, 1), "unit": "molecules/s", "n_gpus": world, "steps": a.steps,
@@ -1261,32 +1292,15 @@ def main():
             "dp_step_parts_us": parts_out(dp_parts, 3),
             "config2_full": None,
             "config": {"workload": "PCQM4Mv2-shaped pretrain step: GIN5x300 + SchNet(6x128f,51g,rc10) + "
-                                   "EBM_node_dot_prod contrastive + SDEModel2Dto3D_02 VE" + (" + SDEModel3Dto2D_node_adj_dense VE" if a.full else "") + "; fwd+bwd+Adam",
+                                   "EBM_node_dot_prod contrastive + SDEModel2Dto3D_02 VE" + (" + SDEModel3Dto2D_node_adj_dense VE" if a.config2 else "") + "; fwd+bwd+Adam",
                        "molecules_per_gpu": a.batch_size, "global_batch": world * a.batch_size,
                        "parallelism": f"dp{world}", "batch_shape": stats, "dropout_p_2Dto3D": 0.1,
                        "launch": launch or (("hipGraph replay, one graph per batch shape (pool of %d shapes)" % len(pool))
                                             if use_graph else "eager"),
                        "stream": stream_info, "eager_ms_per_step": None if eager_ms is None else round(eager_ms, 3),
                        "loss_scalar": float(trainer.log["2Dto3D"]) / max(trainer.steps, 1)},
-            "tail_us": None if in_step.get("tail") is None else round(in_step["tail"], 1),
-            "tail_us_what": "end of the backward chain of the main stream -> end of Adam and of the weight-copy refresh, device "
-                            "stamps inside the captured per-shape step (grouped weight gradients, slab reduction, Adam)",
-            "tail_after_both_streams_us": None if in_step.get("tail_both") is None else round(in_step["tail_both"], 1),
-            "tail_after_both_streams_what": "end of the SECOND stream's work of the backward pass INCLUDING its deferred leaf kernels "
-                                            "(embedding / bond-table gradients, which run beside the grouped weight-gradient launch) -> "
-                                            "end of Adam and of the weight-copy refresh",
-            "tail_after_side_chain_us": None if in_step.get("tail_chain") is None else round(in_step["tail_chain"], 1),
-            "tail_after_side_chain_what": "end of the second stream's backward CHAIN (SchNet's backward, before its leaf kernels) -> "
-                                          "end of the step: with tail_us, how serial the grouped launch + reduction + Adam are",
-            "step_us_device_stamps": None if in_step.get("step") is None else round(in_step["step"], 1),
-            "kernels_per_step": n_kern, "kernels_per_step_not_from_libmsde_hip": n_foreign,
-            "roofline": roof,
-            "roofline_cfconv_pair_filter": roof_filter,
-            "roofline_cfconv_pair_bwd_w": roof_bwd,
-            "roofline_hbm_message_passing": roof_agg,
-            "roofline_forward_schnet_sde2d3d": roof_forward,
-            "roofline_dense_head_node_mlp": roof_head,
         }
+        out.update(extra)
         if c2_ok:
             out["config2_full"] = {
                 "what": "BASELINE.json configs[2]: the FULL pretrain step (contrastive + 2D->3D + 3D->2D dense head, VE; "
@@ -1297,16 +1311,16 @@ def main():
                 "steps": a.steps, "launch": config2["launch"], "stream": config2["stream"],
                 "ms_per_step_per_rank": spread(2, 1e3 / a.steps),
                 "dp_step_parts_us": parts_out(config2.get("dp_step_parts_us"), 7)}
-        elif a.full:
-            out["config2_full"] = {"what": "this line's headline IS the full step (--full)", "ms_per_step": out["ms_per_step"],
+        elif a.config2:
+            out["config2_full"] = {"what": "this line's headline IS the full step (--config2)", "ms_per_step": out["ms_per_step"],
                                    "value": out["value"], "unit": "molecules/s", "n_gpus": world}
         elif config2 is not None:
             out["config2_full"] = config2              # {"error": ...}
         assert all(k in out for k in DP_LINE_KEYS)
-        if world == 1 and not a.no_configs45:
+        if a.full and world == 1 and not a.no_configs45:
             out["config4_sampler"] = config4_sampler(device)
             out["config5_md17"] = config5_md17(device)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.batch_size)
         if a.dump_outputs:
             arrays = dumped.get("stream", dumped.get("pool"))

@@ -1,12 +1,13 @@
 """Alternating A/B of module constants and / or library builds on the bench line, on ONE box, without editing any source.
 
-    python tools/ab_set.py ROUNDS [--full] [--steps N] name1=SET1 name2=SET2 ...
+    python tools/ab_set.py ROUNDS [--config2] [--steps N] name1=SET1 name2=SET2 ...
         SET = comma list of  package.module:ATTR=python-literal,  lib:tools/_build/libmsde_x.so,  arg:<bench.py argument>,  --dp
               (empty: defaults)
     e.g. python tools/ab_set.py 3 units= r5order=moleculesde_amd.slabs:WGRAD_UNIT_ORDER=False r5=lib:tools/_build/libmsde_r5split.so
 
-Each run is a child process (`--child`): it applies the setting after importing the modules, runs bench.main() with the
-secondary measurements off and prints ms_per_step (headline; with --full the full step).  Replaces the sed-based ab_flag*.sh."""
+Each run is a child process (`--child`): it applies the setting after importing the modules, runs bench.main() under
+--full (the line's in-step tail and forward figure are printed too) with the --no_* options on, and prints ms_per_step
+(headline; with --config2 the full step).  Replaces the sed-based ab_flag*.sh."""
 import importlib
 import json
 import os
@@ -43,12 +44,13 @@ if __name__ == "__main__":
         sys.exit(0)
     rounds = int(sys.argv[1])
     rest = sys.argv[2:]
-    full = "--full" in rest
+    config2 = "--config2" in rest
     steps = "300"
     if "--steps" in rest:
         steps = rest[rest.index("--steps") + 1]
     sets = [a.split("=", 1) for a in rest if "=" in a and not a.startswith("--")]
-    bench_args = ["--no_cpu_baseline", "--no_configs45", "--no_pipeline", "--no_config2", "--steps", steps] + (["--full"] if full else [])
+    bench_args = ["--full", "--no_cpu_baseline", "--no_configs45", "--no_pipeline", "--no_config2", "--steps", steps] + \
+        (["--config2"] if config2 else [])
     res = {n: [] for n, _ in sets}
     for r in range(rounds):
         for name, setting in sets:

@@ -6,7 +6,7 @@ set -euo pipefail
 cd "$GRAFT_REPO_ROOT"
 R=${1:-r06}
 mkdir -p gpurun_out/$R
-MSDE_DP_BACKEND=gloo timeout 900 python3 bench.py --gpus 2 --steps 6 --warmup 2 --no_cpu_baseline --no_configs45 \
+MSDE_DP_BACKEND=gloo timeout 900 python3 bench.py --gpus 2 --steps 6 --warmup 2 --full --no_cpu_baseline --no_configs45 \
     > gpurun_out/$R/bench_dp2_gloo_one_gpu.json 2> gpurun_out/$R/bench_dp2_gloo_one_gpu.err || { echo "dp2 rc=$?"; tail -20 gpurun_out/$R/bench_dp2_gloo_one_gpu.err; exit 1; }
 python3 - "$R" <<'PY'
 import json, sys
