@@ -718,6 +718,25 @@ int msde_cl_ebm_bwd(const float* X, const float* Y, const int* perm1, const int*
                     const int* inv1, const int* inv2, const float* rows, const float* g_loss, int N,
                     int D, float invT, float* gX, float* gY, const int* rows_dev, void* stream);
 
+/* do_CL('InfoNCE_dot_prod') in both directions + dual_CL — examples/util.py:23-32,76-79 (called node level from
+ * examples/pretrain_MoleculeSDE.py:137).  S = X Y^T / T over all N rows; Y X^T / T is S^T, so one matrix serves both
+ * directions.  ws: msde_cl_infonce_workspace_floats(N) floats (S [N,N], per-tile row / column partials, lse [2N]); the
+ * backward reads it.  out[0] = loss, out[1] = accuracy (argmax ties go to the lowest index, as torch.argmax).  N and D are
+ * host integers: every row is valid. */
+long long msde_cl_infonce_workspace_floats(int N);
+int msde_cl_infonce_fwd(const float* X, const float* Y, int N, int D, float invT, float* ws, float* out, void* stream);
+int msde_cl_infonce_bwd(const float* X, const float* Y, const float* ws, const float* g_loss, int N, int D, float invT,
+                        float* gX, float* gY, void* stream);
+
+/* do_CL('EBM_dot_prod') in both directions + dual_CL — examples/util.py:16-19,34-50,76-79: the positive <X_i, Y_i> / T and
+ * K = CL_neg_samples deterministic cyclic-shift negatives per direction (cycle_index: row i against row (i + s) mod N,
+ * s = 1..K); 1 <= K < N.  rows [N, 1 + 2K] (p, n1 for s = 1..K, n2 for s = 1..K) feeds the backward.  out[0] = loss,
+ * out[1] = accuracy. */
+int msde_cl_ebm_shift_fwd(const float* X, const float* Y, int N, int D, int K, float invT, float* rows, float* out,
+                          void* stream);
+int msde_cl_ebm_shift_bwd(const float* X, const float* Y, const float* rows, const float* g_loss, int N, int D, int K,
+                          float invT, float* gX, float* gY, void* stream);
+
 /* ------------------------------------------------------------------ normalisation ---------- */
 /* nn.BatchNorm1d in training mode over the rows of X[M,C], optional fused ReLU —
  * molecule_gnn_model.py:17,176-182; SDE_model_2D_to_3D.py:265.  Batch statistics by Welford partials

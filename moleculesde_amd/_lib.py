@@ -132,6 +132,11 @@ SIGNATURES = {
     "msde_combine_losses_ex": [P, P, P, P, F, F, F, F, P, P, P, P, I, P],
     "msde_cl_ebm_fwd": [P, P, P, P, I, I, F, P, P, P, P, P, P],
     "msde_cl_ebm_bwd": [P, P, P, P, P, P, P, P, I, I, F, P, P, P, P],
+    "msde_cl_infonce_workspace_floats": [I],
+    "msde_cl_infonce_fwd": [P, P, I, I, F, P, P, P],
+    "msde_cl_infonce_bwd": [P, P, P, P, I, I, F, P, P, P],
+    "msde_cl_ebm_shift_fwd": [P, P, I, I, I, F, P, P, P],
+    "msde_cl_ebm_shift_bwd": [P, P, P, P, I, I, I, F, P, P, P],
     "msde_bn_workspace_floats": [I, I],
     "msde_colsum": [P, I, I, P, P, P, P],
     "msde_res_layernorm_fwd": [P, P, P, P, I, I, F, P, P, P, P],
@@ -226,7 +231,8 @@ _RESTYPE = {"msde_target_arch": ctypes.c_char_p, "msde_linear_bwd_w_workspace_by
             "msde_gin_aggregate_bwd_tab_workspace_floats": ctypes.c_longlong,
             "msde_reduce_slabs_chunks": ctypes.c_longlong, "msde_escore_mol_saved_floats": ctypes.c_longlong,
             "msde_escore_mol_score_scratch_floats": ctypes.c_longlong,
-            "msde_escore_mol_slab_floats": ctypes.c_longlong}
+            "msde_escore_mol_slab_floats": ctypes.c_longlong,
+            "msde_cl_infonce_workspace_floats": ctypes.c_longlong}
 
 _lib = None
 

@@ -1495,6 +1495,78 @@ def contrastive_ebm(X, Y, perm1, perm2, T):
     return loss, acc
 
 
+class _ContrastiveInfoNCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, Y, T):
+        X, Y = _f32(X), _f32(Y)
+        N, D = X.shape
+        ws = torch.empty(int(_lib.load().msde_cl_infonce_workspace_floats(N)), dtype=torch.float32, device=X.device)
+        out = torch.empty(2, dtype=torch.float32, device=X.device)
+        _lib.call("msde_cl_infonce_fwd", _p(X), _p(Y), N, D, 1.0 / float(T), _p(ws), _p(out), _stream())
+        ctx.save_for_backward(X, Y, ws)
+        ctx.invT = 1.0 / float(T)
+        loss, acc = out[0], out[1]
+        ctx.mark_non_differentiable(acc)
+        ctx.set_materialize_grads(False)
+        return loss, acc
+
+    @staticmethod
+    def backward(ctx, g_loss, g_acc):
+        if g_loss is None:
+            return None, None, None
+        X, Y, ws = ctx.saved_tensors
+        N, D = X.shape
+        gX, gY = torch.empty_like(X), torch.empty_like(Y)
+        g = _f32(g_loss).reshape(1)
+        _lib.call("msde_cl_infonce_bwd", _p(X), _p(Y), _p(ws), _p(g), N, D, ctx.invT, _p(gX), _p(gY), _stream())
+        return gX, gY, None
+
+
+def contrastive_infonce(X, Y, T):
+    """dual_CL with 'InfoNCE_dot_prod' (examples/util.py:23-32,76-79) over all rows of X and Y: returns (loss, accuracy).
+    The [N, N] logits live in a workspace the backward reads (N^2 + O(N) floats, held until the backward has run)."""
+    loss, acc = _ContrastiveInfoNCE.apply(X, Y, T)
+    return loss, acc
+
+
+class _ContrastiveEBMShift(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, Y, K, T):
+        X, Y = _f32(X), _f32(Y)
+        N, D = X.shape
+        rows = torch.empty(N, 1 + 2 * K, dtype=torch.float32, device=X.device)
+        out = torch.empty(2, dtype=torch.float32, device=X.device)
+        _lib.call("msde_cl_ebm_shift_fwd", _p(X), _p(Y), N, D, K, 1.0 / float(T), _p(rows), _p(out), _stream())
+        ctx.save_for_backward(X, Y, rows)
+        ctx.K, ctx.invT = K, 1.0 / float(T)
+        loss, acc = out[0], out[1]
+        ctx.mark_non_differentiable(acc)
+        ctx.set_materialize_grads(False)
+        return loss, acc
+
+    @staticmethod
+    def backward(ctx, g_loss, g_acc):
+        if g_loss is None:
+            return None, None, None, None
+        X, Y, rows = ctx.saved_tensors
+        N, D = X.shape
+        gX, gY = torch.empty_like(X), torch.empty_like(Y)
+        g = _f32(g_loss).reshape(1)
+        _lib.call("msde_cl_ebm_shift_bwd", _p(X), _p(Y), _p(rows), _p(g), N, D, ctx.K, ctx.invT, _p(gX), _p(gY),
+                  _stream())
+        return gX, gY, None, None
+
+
+def contrastive_ebm_shift(X, Y, K, T):
+    """dual_CL with 'EBM_dot_prod' (examples/util.py:16-19,34-50,76-79): K = CL_neg_samples cyclic-shift negatives per
+    direction (row i against row (i + s) mod N, s = 1..K).  Returns (loss, accuracy).  Requires 1 <= K < N."""
+    K, N = int(K), int(X.shape[0])
+    if not 1 <= K < N:
+        raise ValueError(f"EBM_dot_prod needs 1 <= CL_neg_samples < N (the cyclic shifts of cycle_index): K={K}, N={N}")
+    loss, acc = _ContrastiveEBMShift.apply(X, Y, K, T)
+    return loss, acc
+
+
 # ------------------------------------------------------------------------------------------------
 # normalisation
 # ------------------------------------------------------------------------------------------------

@@ -48,6 +48,7 @@ def add_hot_path_flags(parser):
     a("--PaiNN_n_rbf", type=int, default=20)
     a("--PaiNN_readout", type=str, default="add", choices=["mean", "add"])
     a("--CL_similarity_metric", type=str, default="InfoNCE_dot_prod")
+    a("--CL_neg_samples", type=int, default=1)
     a("--T", type=float, default=0.1)
     a("--normalize", dest="normalize", action="store_true")
     a("--no_normalize", dest="normalize", action="store_false")
@@ -196,10 +197,48 @@ def make_optimizer(args, models):
     return FlatAdam(groups, betas=(0.9, 0.999), eps=1e-8, weight_decay=args.decay)
 
 
+def cycle_index(num, shift):
+    """examples/util.py:16-19: row i -> row (i + shift) mod num (for 0 < shift < num)."""
+    return (torch.arange(num) + shift) % num
+
+
+def _neg_samples(args, n):
+    K = int(getattr(args, "CL_neg_samples", 1))
+    if not 1 <= K < n:
+        raise ValueError(f"EBM_dot_prod needs 1 <= CL_neg_samples < N (the cyclic shifts of cycle_index): K={K}, N={n}")
+    return K
+
+
+# the metrics whose loss draws random negatives (one permutation per direction); the other two draw nothing
+DRAWS_NEGATIVES = ("EBM_node_dot_prod",)
+# the metrics the capacity-bucket (padded) paths run: the kernels of the other two take a host row count
+BUCKET_CL_METRICS = ("EBM_node_dot_prod",)
+
+
 def do_CL(X, Y, args, noise, neg_index=None):
-    """'EBM_node_dot_prod' branch of examples/util.py:52-68 (the metric of the README command)."""
-    if args.CL_similarity_metric != "EBM_node_dot_prod":
-        raise NotImplementedError(args.CL_similarity_metric)
+    """examples/util.py:22-73 as torch ops (the CPU path and the tests' reference for the kernels); the accuracy stays a
+    tensor.  'InfoNCE_dot_prod': cross entropy of X Y^T / T against the diagonal over all rows; 'EBM_dot_prod': BCE on the
+    positives and on CL_neg_samples cyclic shifts of Y; 'EBM_node_dot_prod': BCE with one random permutation of Y."""
+    m = args.CL_similarity_metric
+    if m == "InfoNCE_dot_prod":
+        B = X.size(0)
+        logits = torch.mm(X, Y.t()) / args.T
+        labels = torch.arange(B, device=X.device)
+        loss = F.cross_entropy(logits, labels)
+        acc = (logits.argmax(dim=1) == labels).sum().to(logits.dtype) / B
+        return loss, acc.detach()
+    if m == "EBM_dot_prod":
+        K = _neg_samples(args, len(Y))
+        neg_Y = torch.cat([Y[cycle_index(len(Y), i + 1).to(Y.device)] for i in range(K)], dim=0)
+        neg_X = X.repeat((K, 1))
+        pred_pos = torch.sum(X * Y, dim=1) / args.T
+        pred_neg = torch.sum(neg_X * neg_Y, dim=1) / args.T
+        loss_pos = F.binary_cross_entropy_with_logits(pred_pos, torch.ones_like(pred_pos))
+        loss_neg = F.binary_cross_entropy_with_logits(pred_neg, torch.zeros_like(pred_neg))
+        acc = (torch.sum(pred_pos > 0).float() + torch.sum(pred_neg < 0).float()) / (len(pred_pos) + len(pred_neg))
+        return loss_pos + K * loss_neg, acc.detach()
+    if m != "EBM_node_dot_prod":
+        raise NotImplementedError(m)
     if neg_index is None:
         neg_index = noise.randperm(len(Y), Y.device)
     neg_Y = Y[neg_index]
@@ -212,13 +251,21 @@ def do_CL(X, Y, args, noise, neg_index=None):
 
 
 def dual_CL(X, Y, args, noise, neg_indices=(None, None)):
-    """examples/util.py:76-79; the accuracy stays a device scalar (no sync).  On the HIP device both
-    directions run as one fused kernel pair (csrc/contrastive.hip)."""
-    if X.is_cuda and args.CL_similarity_metric == "EBM_node_dot_prod" and USE_FUSED_CL:
-        n1 = neg_indices[0] if neg_indices[0] is not None else noise.randperm(len(Y), Y.device)
-        n2 = neg_indices[1] if neg_indices[1] is not None else noise.randperm(len(X), X.device)
+    """examples/util.py:76-79; the accuracy stays a device scalar (no sync).  On the HIP device both directions run as one
+    fused kernel pair per metric (csrc/contrastive.hip, csrc/contrastive_infonce.hip).  Under data parallelism every rank's
+    loss runs over its own atoms only: InfoNCE's negatives are the other atoms of the rank's batch, as the reference's
+    are those of its batch (no all-gather)."""
+    m = args.CL_similarity_metric
+    if X.is_cuda and USE_FUSED_CL:
         from . import hip
-        return hip.contrastive_ebm(X, Y, n1, n2, args.T)
+        if m == "EBM_node_dot_prod":
+            n1 = neg_indices[0] if neg_indices[0] is not None else noise.randperm(len(Y), Y.device)
+            n2 = neg_indices[1] if neg_indices[1] is not None else noise.randperm(len(X), X.device)
+            return hip.contrastive_ebm(X, Y, n1, n2, args.T)
+        if m == "InfoNCE_dot_prod":
+            return hip.contrastive_infonce(X, Y, args.T)
+        if m == "EBM_dot_prod":
+            return hip.contrastive_ebm_shift(X, Y, _neg_samples(args, len(Y)), args.T)
     l1, a1 = do_CL(X, Y, args, noise, neg_indices[0])
     l2, a2 = do_CL(Y, X, args, noise, neg_indices[1])
     return (l1 + l2) / 2, (a1 + a2) / 2
@@ -334,10 +381,11 @@ class Trainer:
         # both happen before any encoder runs so that the coordinate-only branch of the 2D->3D model can start
         # right away on its own stream (neither encoder draws random numbers on this path)
         negs = (None, None)
+        draws = self.coeff_cl > 0 and a.CL_similarity_metric in DRAWS_NEGATIVES     # the other metrics draw nothing
         # device noise: the permutation kernel (20 us, read 1.2 ms later by the contrastive loss) runs at the head of the
         # SECOND stream instead of at the head of the main chain; host call order (= the reference's draw order) unchanged
-        negs_on_side = self.coeff_cl > 0 and self.overlap_streams and not getattr(self.noise, "replay", False)
-        if self.coeff_cl > 0 and not negs_on_side:
+        negs_on_side = draws and self.overlap_streams and not getattr(self.noise, "replay", False)
+        if draws and not negs_on_side:
             n = batch.x.size(0)
             negs = self.noise.randperm_pair(n, batch.x.device)
         if (a.SDE_coeff_generative_2Dto3D > 0 and GEOMETRY_ON_SIDE and self.overlap_streams
@@ -759,10 +807,20 @@ class Trainer:
         from .bucket import Bucket
         return Bucket(caps, self.device)
 
+    def check_bucket_metric(self):
+        """The capacity-bucket paths (padded rows) run the contrastive term of BUCKET_CL_METRICS only."""
+        m = self.args.CL_similarity_metric
+        if self.coeff_cl > 0 and m not in BUCKET_CL_METRICS:
+            raise NotImplementedError(
+                f"CL_similarity_metric={m} is not supported on capacity-bucket (padded) batches (capture_bucket, StreamRunner, "
+                "BucketPipeline): train it on exact-size batches instead (Trainer.step, or Trainer.capture + step_graph; "
+                "pretrain --eager)")
+
     def capture_bucket(self, bk, warm_blob, eager_steps=2, split_plan=False):
         """Warm up on one raw batch (sizes the workspaces), then capture {device-side plan construction + step} for
         the bucket's capacities.  Afterwards every batch that fits the capacities is `step_bucket(bk, blob)`: one
         copy of its raw blob + one graph replay, no per-batch host work."""
+        self.check_bucket_metric()
         bk.load(warm_blob)
         bk.build_plan_on_device()
         ok, sizes = bk.check()
@@ -894,6 +952,7 @@ class StreamRunner:
         """The loss coefficients are launch arguments baked into the graph: after a change (the contrastive skip epochs of
         pretrain_MoleculeSDE.py:339-344) the step is captured again on the batch the bucket holds."""
         if self._coeffs() != self._captured_coeffs:
+            self.tr.check_bucket_metric()
             # (the superseded graph is parked, not destroyed: freeing a graph of the shared memory pool while another capture
             # into that pool follows trips an allocator assertion in this torch build; it is a few hundred nodes)
             self._parked = getattr(self, "_parked", []) + [self.tr._graphs.pop(id(self.bk.batch), None)]
@@ -1005,6 +1064,10 @@ def main(argv=None):
     p.add_argument("--synthetic_pool", type=int, default=64, help="distinct synthetic batches an epoch cycles over")
     p.add_argument("--eager", action="store_true", help="launch every kernel from the host (no hipGraph, no bucket)")
     args = p.parse_args(argv)
+    if not args.eager and args.SDE_coeff_contrastive > 0 and args.CL_similarity_metric not in BUCKET_CL_METRICS:
+        print(f"CL_similarity_metric={args.CL_similarity_metric}: the captured bucket step takes EBM_node_dot_prod only, "
+              "training on resident exact-size batches (--eager)", flush=True)
+        args.eager = True
     rank, world, local = dp.init_from_env("cuda")
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
