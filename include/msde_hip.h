@@ -982,6 +982,25 @@ int msde_qm9_head_train(const float* out, int ldo, int B, int D, const float* W,
 int msde_qm9_head_eval(const float* out, int ldo, int B, int D, const float* W, const float* b, const float* y, int ldy,
                        float mean, float std, float* pred, double* acc, void* stream);
 
+/* ------------------------------------------------------------------ MD17 epochs ------------ */
+/* examples/finetune_MD17.py:34-142 around the captured force step.  One workgroup each, fixed-order sums: bitwise repeatable.
+ *   msde_md17_eval_accumulate: eval() (:93-142) on predicted energies E [B], targets y [B], dE [n3] (d energy / d positions,
+ *     force = -dE) and force targets f [n3]: acc[0] += sum |E - y| (difference in fp32; a NaN propagates), acc[1] += B,
+ *     acc[2] += sum |-dE - f| over the entries whose -dE is not NaN (force[~mask], :127-130), acc[3] += their count (fp64).
+ *   msde_l1_energy_force_loss_acc: msde_l1_energy_force_loss, the same arithmetic in the same order (bitwise the same loss,
+ *     gE and gdE), and loss_acc[0] += loss (fp64 epoch sum).
+ *   msde_md17_gather_batch: a split held on the device (pos [M, row], y [M], force [M, row] with row = 3 * atoms; force may be
+ *     NULL with f_dst): k = counter[0], batch row r < B is split row j = k * stride + r (stride >= B: the full batch size,
+ *     also for the short last batch), through perm[j] (int32, may be NULL); copied into pos_dst [B, row], y_dst [B],
+ *     f_dst [B, row].  Rows with j >= M (or perm[j] outside [0, M)) are not read; their destination is left as it was.
+ *     Then counter[0] = k + 1. */
+int msde_md17_eval_accumulate(const float* E, const float* y, int B, const float* dE, const float* f, int n3, double* acc,
+                              void* stream);
+int msde_l1_energy_force_loss_acc(const float* E, const float* y, int B, const float* dE, const float* f, int n3, float fsign,
+                                  float ce, float cf, float* loss, float* gE, float* gdE, double* loss_acc, void* stream);
+int msde_md17_gather_batch(const float* pos, const float* y, const float* force, int M, int row, const int* perm, int* counter,
+                           int stride, int B, float* pos_dst, float* y_dst, float* f_dst, void* stream);
+
 /* ------------------------------------------------------------------ optimiser -------------- */
 /* torch.optim.Adam step over a flat parameter buffer with per-element lr via segment table —
  * examples/pretrain_MoleculeSDE.py:331-337,156.  seg_end[S] (exclusive ends), seg_lr[S].

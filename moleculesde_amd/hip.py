@@ -1830,6 +1830,47 @@ def qm9_head_eval(out, W, b, y, mean, std, acc, pred=None):
     return pred
 
 
+
+# ---- MD17 epochs (csrc/md17.hip) -----------------------------------------------------------------------------------
+def md17_eval_accumulate(E, y, dE, f, acc):
+    """eval() of finetune_MD17.py (:93-142) on one batch, added to the device fp64 acc[4]: sum |E - y|, B, sum |-dE - f| over
+    the entries whose predicted force -dE is not NaN, and their count (msde_md17_eval_accumulate)."""
+    E, y, dE, f = _f32(E), _f32(y), _f32(dE), _f32(f)
+    assert E.numel() == y.numel() and dE.numel() == f.numel()
+    assert acc.dtype == torch.float64 and acc.numel() >= 4 and acc.is_contiguous()
+    _lib.call("msde_md17_eval_accumulate", _p(E), _p(y), E.numel(), _p(dE), _p(f), dE.numel(), _p(acc), _stream())
+    return acc
+
+
+def l1_energy_force_loss_acc(E, y, dE, f, fsign, ce, cf, loss_acc):
+    """msde_l1_energy_force_loss (same arithmetic, same order: a bitwise equal loss) plus loss_acc[0] += loss (fp64).
+    Returns (loss [1], d loss / d E [B], d loss / d dE [n3])."""
+    E, y, dE, f = _f32(E), _f32(y), _f32(dE), _f32(f)
+    assert E.numel() == y.numel() and dE.numel() == f.numel()
+    assert loss_acc.dtype == torch.float64
+    loss = torch.empty(1, dtype=torch.float32, device=E.device)
+    g_e, g_d = torch.empty_like(E), torch.empty_like(dE)
+    _lib.call("msde_l1_energy_force_loss_acc", _p(E), _p(y), E.numel(), _p(dE), _p(f), dE.numel(), float(fsign), float(ce),
+              float(cf), _p(loss), _p(g_e), _p(g_d), _p(loss_acc), _stream())
+    return loss, g_e, g_d
+
+
+def md17_gather_batch(pos, y, force, perm, counter, stride, pos_dst, y_dst, f_dst):
+    """Batch counter[0] of a device-resident split (pos [M, NA, 3], y [M], force [M, NA, 3] or None) into static buffers
+    (pos_dst [B * NA, 3], y_dst [B], f_dst [B * NA, 3]): split rows counter[0] * stride + r (through perm [M] int32 when
+    given), rows past the split's end left as they were; then counter[0] += 1 (msde_md17_gather_batch)."""
+    M = pos.size(0)
+    row = pos[0].numel()
+    B = y_dst.numel()
+    for t in (pos, y, force, pos_dst, y_dst, f_dst):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    assert y.numel() == M and pos_dst.numel() == B * row and (force is None) == (f_dst is None)
+    assert force is None or (force.numel() == M * row and f_dst.numel() == B * row)
+    assert counter.dtype == torch.int32 and stride >= B
+    assert perm is None or (perm.dtype == torch.int32 and perm.numel() == M and perm.is_contiguous())
+    _lib.call("msde_md17_gather_batch", _p(pos), _p(y), _p(force), M, row, _p(perm), _p(counter), int(stride), B, _p(pos_dst),
+              _p(y_dst), _p(f_dst), _stream())
+
 class _MulAdd(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, c):
