@@ -653,6 +653,16 @@ int msde_dense_node_gcn_fwd(const float* XW0, const float* AC, const int* mol_pt
 int msde_dense_node_gcn_bwd(const float* gXS, int ldg, const float* XS, int ldxs, const float* AC,
                             const int* mol_ptr, const int* pair_ptr, const float* Wl, int B, int n_max,
                             float* GP, float* MM, void* stream);
+/* The same chain for SDEModel3Dto2D_node_adj_dense_03, whose layers read cat(x_l, E3): W_l is [16 + F][16] and its x_l rows
+ * (the first 16) start wstride floats apart (256 reproduces the calls above); PE [N, ldpe >= 48] (or NULL: none) holds the
+ * conditioning terms E3 W_E,l of layers 1..3 in column blocks of 16, added to x_l W_l before the adjacency product.  The
+ * backward's MM is the gradient of the whole product: the E3 rows' gradients (E3^T MM_l, MM_l W_E,l^T) are GEMMs outside. */
+int msde_dense_node_gcn_fwd_ex(const float* XW0, const float* AC, const int* mol_ptr, const int* pair_ptr,
+                               const float* Wl, int wstride, const float* bl, const float* PE, int ldpe, int B, int n_max,
+                               float* XS, int ldxs, void* stream);
+int msde_dense_node_gcn_bwd_ex(const float* gXS, int ldg, const float* XS, int ldxs, const float* AC,
+                               const int* mol_ptr, const int* pair_ptr, const float* Wl, int wstride, int B, int n_max,
+                               float* GP, float* MM, void* stream);
 /* Last Linear(F2, 1) of the pair MLP + diagonal / flag masks + score = -net / std + both losses (:86-94,157-179).
  * out[0] = loss_x, out[1] = loss_adj; scale_* = 1/(B Nmax ncls), 1/(B Nmax^2) (reduce_mean) or 0.5/B;
  * residuals res_adj [P], res_x [N, MSDE_DENSE_XP_LD] are kept for the backward; part = [B * MSDE_DENSE_LOSS_SPLITS][2]

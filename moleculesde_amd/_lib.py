@@ -104,6 +104,8 @@ SIGNATURES = {
                                   P],
     "msde_dense_node_gcn_fwd": [P, P, P, P, P, P, I, I, P, I, P],
     "msde_dense_node_gcn_bwd": [P, I, P, I, P, P, P, P, I, I, P, P, P],
+    "msde_dense_node_gcn_fwd_ex": [P, P, P, P, P, I, P, P, I, I, I, P, I, P],
+    "msde_dense_node_gcn_bwd_ex": [P, I, P, I, P, P, P, P, I, I, I, P, P, P],
     "msde_dense_loss_fwd": [P, I, P, P, P, P, P, P, P, P, P, I, I, F, F, F, P, P, P, P, P, P],
     "msde_dense_loss_bwd": [P, P, P, P, P, I, P, P, P, P, P, I, I, F, F, F, P, P, P, P, P],
     "msde_dense_pc_init": [P, P, P],

@@ -945,17 +945,22 @@ extern "C" int msde_dense_edge_layer_bwd(const float* QK, const float* XV, const
 // ================================================================================================ node GCN chain
 // x_{l+1} = tanh(An (x_l W_l) + b_l), l = 0..3, An from the perturbed adjacency (channel 0 of the pair buffer);
 // x_0 W_0 comes in as XW0 [N,16] (a GEMM), W_1..3 are [16 in][16 out].  Output: XS = [x_1|x_2|x_3|x_4], row stride ldxs.
+// SDEModel3Dto2D_node_adj_dense_03 (NodeNetwork_dense_03, node_network_dense.py:91-155): layer l reads cat(x_l, E3), so its
+// weight is [16 + F][16] -- rows 0..15 (read here, `wstride` floats apart) act on x_l, the rest on E3 -- and COND adds the
+// conditioning term PE[:, 16 (l-1) ..] = E3 W_E,l (one GEMM before the launch) to x_l W_l ahead of the An product.
+template <bool COND>
 __global__ void __launch_bounds__(256)
 dense_node_gcn_fwd_kernel(const float* __restrict__ XW0, const float* __restrict__ AC, const int* __restrict__ mol_ptr,
-                          const int* __restrict__ pair_ptr, const float* __restrict__ Wl /* [3][16][16] */,
-                          const float* __restrict__ bl /* [4][16] */, float* __restrict__ XS, int ldxs) {
+                          const int* __restrict__ pair_ptr, const float* __restrict__ Wl /* [3][wstride], 16 x 16 used */,
+                          int wstride, const float* __restrict__ bl /* [4][16] */, const float* __restrict__ PE, int ldpe,
+                          float* __restrict__ XS, int ldxs) {
   __shared__ float An[DH_NMAX][DH_NMAX + 1];
   __shared__ float xa[DH_NMAX][17], xb[DH_NMAX][17];
   __shared__ float rn[DH_NMAX];
   __shared__ float W[3][16][17];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int a0 = mol_ptr[b], n = mol_ptr[b + 1] - a0, q0 = pair_ptr[b];
-  for (int e = tid; e < 3 * 256; e += 256) W[e >> 8][(e >> 4) & 15][e & 15] = Wl[e];
+  for (int e = tid; e < 3 * 256; e += 256) W[e >> 8][(e >> 4) & 15][e & 15] = Wl[(size_t)(e >> 8) * wstride + (e & 255)];
   for (int p = tid; p < n * n; p += 256) {
     const int i = p / n, j = p - i * n;
     An[i][j] = (i == j) ? 1.f : AC[(size_t)(q0 + p) * DH_AC];
@@ -987,7 +992,7 @@ dense_node_gcn_fwd_kernel(const float* __restrict__ XW0, const float* __restrict
     if (l < 3) {
       for (int e = tid; e < n * 16; e += 256) {
         const int i = e >> 4, f = e & 15;
-        float s = 0.f;
+        float s = COND ? PE[(size_t)(a0 + i) * ldpe + 16 * l + f] : 0.f;
 #pragma unroll
         for (int k = 0; k < 16; ++k) s = fmaf(xb[i][k], W[l][k][f], s);
         xa[i][f] = s;
@@ -998,11 +1003,12 @@ dense_node_gcn_fwd_kernel(const float* __restrict__ XW0, const float* __restrict
 }
 
 // backward of the chain: gXS [N, 64 (ld)] -> GP [N,64] = dL/d(pre-activation of layer l) in block l (bias gradients =
-// column sums), MM [N,64] = An^T GP per block (block 0 = dL/d(x_0 W_0); blocks 1..3: weight gradients x_l^T MM_l)
+// column sums), MM [N,64] = An^T GP per block (block 0 = dL/d(x_0 W_0); blocks 1..3: weight gradients x_l^T MM_l).
+// MM is the gradient of the whole product cat(x_l, E3) W_l of _03 too: only the x_l rows of W_l (stride wstride) are read here.
 __global__ void __launch_bounds__(256)
 dense_node_gcn_bwd_kernel(const float* __restrict__ gXS, int ldg, const float* __restrict__ XS, int ldxs,
                           const float* __restrict__ AC, const int* __restrict__ mol_ptr,
-                          const int* __restrict__ pair_ptr, const float* __restrict__ Wl, float* __restrict__ GP,
+                          const int* __restrict__ pair_ptr, const float* __restrict__ Wl, int wstride, float* __restrict__ GP,
                           float* __restrict__ MM) {
   __shared__ float An[DH_NMAX][DH_NMAX + 1];
   __shared__ float gx[DH_NMAX][17], gp[DH_NMAX][17], mm[DH_NMAX][17];
@@ -1010,7 +1016,7 @@ dense_node_gcn_bwd_kernel(const float* __restrict__ gXS, int ldg, const float* _
   __shared__ float W[3][16][17];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int a0 = mol_ptr[b], n = mol_ptr[b + 1] - a0, q0 = pair_ptr[b];
-  for (int e = tid; e < 3 * 256; e += 256) W[e >> 8][(e >> 4) & 15][e & 15] = Wl[e];
+  for (int e = tid; e < 3 * 256; e += 256) W[e >> 8][(e >> 4) & 15][e & 15] = Wl[(size_t)(e >> 8) * wstride + (e & 255)];
   for (int p = tid; p < n * n; p += 256) {
     const int i = p / n, j = p - i * n;
     An[i][j] = (i == j) ? 1.f : AC[(size_t)(q0 + p) * DH_AC];
@@ -1058,14 +1064,38 @@ dense_node_gcn_bwd_kernel(const float* __restrict__ gXS, int ldg, const float* _
   }
 }
 
+extern "C" int msde_dense_node_gcn_fwd_ex(const float* XW0, const float* AC, const int* mol_ptr, const int* pair_ptr,
+                                          const float* Wl, int wstride, const float* bl, const float* PE, int ldpe, int B,
+                                          int n_max, float* XS, int ldxs, void* stream) {
+  if (B < 0 || !XW0 || !AC || !mol_ptr || !pair_ptr || !Wl || !bl || !XS || ldxs < 64 || wstride < 256) return MSDE_EINVAL;
+  if (PE && ldpe < 48) return MSDE_EINVAL;
+  if (n_max > DH_NMAX) return MSDE_EUNSUP;
+  if (B == 0) return 0;
+  if (PE)
+    MSDE_LAUNCH(dense_node_gcn_fwd_kernel<true>, dim3(B), dim3(256), 0, as_stream(stream), XW0, AC, mol_ptr, pair_ptr, Wl,
+                wstride, bl, PE, ldpe, XS, ldxs);
+  else
+    MSDE_LAUNCH(dense_node_gcn_fwd_kernel<false>, dim3(B), dim3(256), 0, as_stream(stream), XW0, AC, mol_ptr, pair_ptr, Wl,
+                wstride, bl, PE, ldpe, XS, ldxs);
+  MSDE_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int msde_dense_node_gcn_fwd(const float* XW0, const float* AC, const int* mol_ptr, const int* pair_ptr,
                                        const float* Wl, const float* bl, int B, int n_max, float* XS, int ldxs,
                                        void* stream) {
-  if (B < 0 || !XW0 || !AC || !mol_ptr || !pair_ptr || !Wl || !bl || !XS || ldxs < 64) return MSDE_EINVAL;
+  return msde_dense_node_gcn_fwd_ex(XW0, AC, mol_ptr, pair_ptr, Wl, 256, bl, nullptr, 0, B, n_max, XS, ldxs, stream);
+}
+
+extern "C" int msde_dense_node_gcn_bwd_ex(const float* gXS, int ldg, const float* XS, int ldxs, const float* AC,
+                                          const int* mol_ptr, const int* pair_ptr, const float* Wl, int wstride, int B,
+                                          int n_max, float* GP, float* MM, void* stream) {
+  if (B < 0 || !gXS || !XS || !AC || !mol_ptr || !pair_ptr || !Wl || !GP || !MM || ldg < 64 || ldxs < 64 || wstride < 256)
+    return MSDE_EINVAL;
   if (n_max > DH_NMAX) return MSDE_EUNSUP;
   if (B == 0) return 0;
-  MSDE_LAUNCH(dense_node_gcn_fwd_kernel, dim3(B), dim3(256), 0, as_stream(stream), XW0, AC, mol_ptr, pair_ptr, Wl, bl, XS,
-              ldxs);
+  MSDE_LAUNCH(dense_node_gcn_bwd_kernel, dim3(B), dim3(256), 0, as_stream(stream), gXS, ldg, XS, ldxs, AC, mol_ptr, pair_ptr,
+              Wl, wstride, GP, MM);
   MSDE_CHECK_LAUNCH();
   return 0;
 }
@@ -1073,13 +1103,7 @@ extern "C" int msde_dense_node_gcn_fwd(const float* XW0, const float* AC, const 
 extern "C" int msde_dense_node_gcn_bwd(const float* gXS, int ldg, const float* XS, int ldxs, const float* AC,
                                        const int* mol_ptr, const int* pair_ptr, const float* Wl, int B, int n_max,
                                        float* GP, float* MM, void* stream) {
-  if (B < 0 || !gXS || !XS || !AC || !mol_ptr || !pair_ptr || !Wl || !GP || !MM || ldg < 64 || ldxs < 64) return MSDE_EINVAL;
-  if (n_max > DH_NMAX) return MSDE_EUNSUP;
-  if (B == 0) return 0;
-  MSDE_LAUNCH(dense_node_gcn_bwd_kernel, dim3(B), dim3(256), 0, as_stream(stream), gXS, ldg, XS, ldxs, AC, mol_ptr, pair_ptr,
-              Wl, GP, MM);
-  MSDE_CHECK_LAUNCH();
-  return 0;
+  return msde_dense_node_gcn_bwd_ex(gXS, ldg, XS, ldxs, AC, mol_ptr, pair_ptr, Wl, 256, B, n_max, GP, MM, stream);
 }
 
 // ================================================================================================ losses

@@ -12,6 +12,11 @@ Layout (see csrc/dense_head.hip): atoms in batch order; pairs of molecule b at r
                  [N, 2F+64]), the two embedding products write adjacent column blocks
   AC [P, 32]     columns 0-1 perturbed adjacency and its square, 2..29 the edge layers' outputs = the concatenation the
                  final pair MLP reads (:81-84)
+SDEModel3Dto2D_node_adj_dense_03 (:352-521) is _02 whose score-network layers all read cat(x_l, E3), E3 = embedding_3D(h) =
+XC[:, :F] (already there): every such product is x_l W_x + E3 W_E -- the second segment of the msde_gemm_ex launch that
+computes x_l W_x, or (node GCN layers 1-3) the term PE = E3 [W_E,1|W_E,2|W_E,3] that msde_dense_node_gcn_fwd_ex adds.  In
+the backward the E3 side of every pre-activation gradient, times W_E^T, accumulates into gXC[:, :F] (embedding_3D's output
+gradient), and the W_E weight gradients E3^T g are further column / row blocks of the same parameter gradients.
 """
 import ctypes
 import types
@@ -115,20 +120,29 @@ def _edge_struct(t):
 
 
 # ------------------------------------------------------------------------------------------------ edge network
-def edge_forward(cfg, x0, AC, flags, chans, offs, T):
+def edge_forward(cfg, x0, AC, flags, chans, offs, T, e3=None):
     """x0 [N, F] (may be a column block), AC columns 0..1 filled.  T: edge_net_tensors.  Returns the saved state; the
-    pair MLP's last hidden layer (G2, ZG2) is in it (its Linear(60, 1) belongs to the loss kernel)."""
+    pair MLP's last hidden layer (G2, ZG2) is in it (its Linear(60, 1) belongs to the loss kernel).  e3 [N, F3] (_03): the
+    q / k / v products of every layer read cat(x, e3) -- their weights have F + F3 inputs, the last F3 act on e3."""
     dev, N, P, B = x0.device, cfg.N, cfg.P, cfg.B
-    sv = types.SimpleNamespace(layers=[], x0=x0)
+    sv = types.SimpleNamespace(layers=[], x0=x0, e3=e3)
     x = x0
     for l, (C, CO) in enumerate(chans):
         t = T[16 * l:16 * l + 16]
         F = x.size(1)
         W2 = 2 * C * 32
         H, QK, XV = _empty(N, W2, device=dev), _empty(N, W2, device=dev), _empty(N, 16 * C, device=dev)
-        hip.gemm_ex(x, t[0], H, bias=t[1], act="tanh")
+        if e3 is None:
+            hip.gemm_ex(x, t[0], H, bias=t[1], act="tanh")
+        else:
+            hip.gemm_ex(x, t[0][:, :F], H, bias=t[1], act="tanh", A2=e3, B2=t[0][:, F:])
         hip.gemm_ex(H, t[2], QK, bias=t[3], groups=2 * C, group_strides=dict(a=32, b=1024, bias=32, c=32), N=32, K=32)
-        hip.gemm_ex(x, t[4], XV, b_kmajor=True, groups=C, group_strides=dict(b=F * 16, c=16), N=16, K=F)
+        if e3 is None:
+            hip.gemm_ex(x, t[4], XV, b_kmajor=True, groups=C, group_strides=dict(b=F * 16, c=16), N=16, K=F)
+        else:           # channel c's weight: rows c (F + F3) .. + F act on x, the next F3 rows on e3 (b_gs applies to both)
+            FW = F + e3.size(1)
+            hip.gemm_ex(x, t[4], XV, b_kmajor=True, groups=C, group_strides=dict(b=FW * 16, c=16), N=16, K=F,
+                        A2=e3, B2=t[4][F:], K2=e3.size(1))
         xo, IN = _empty(N, 16, device=dev), _empty(P, 2 * C, device=dev)
         H1, H2 = _empty(P, 16, device=dev), _empty(P, 16, device=dev)
         xcat, Hmc = _empty(N, 16 * C, device=dev), _empty(N, 16, device=dev)
@@ -148,10 +162,23 @@ def edge_forward(cfg, x0, AC, flags, chans, offs, T):
     return sv
 
 
-def edge_backward(cfg, sv, AC, flags, chans, offs, T, gS, gZG2, gx0, gx0_accumulate, need_gadj0=False, gAC_out=None):
+def _edge_v_wgrad_cond(x, e3, gXV, C, F):
+    """Gradient of the C stacked func_v weights of an _03 edge layer, [C (F + F3), 16] ([in, out] layout): channel c's rows are
+    x^T gXV_c then e3^T gXV_c -- two products whose column blocks the slab reduction writes in place."""
+    F3 = e3.size(1)
+    FW = F + F3
+    gWv = _empty(C * FW, 16, device=x.device)
+    slabs.weight_grad_blocks(x, gXV, False, [(16 * c, 16, gWv[c * FW:c * FW + F], 0) for c in range(C)])
+    slabs.weight_grad_blocks(e3, gXV, False, [(16 * c, 16, gWv[c * FW + F:(c + 1) * FW], 0) for c in range(C)])
+    return gWv
+
+
+def edge_backward(cfg, sv, AC, flags, chans, offs, T, gS, gZG2, gx0, gx0_accumulate, need_gadj0=False, gAC_out=None, ge3=None):
     """gS [P] / gZG2 [P, 60]: gradients of the pair MLP's scalar output / last hidden pre-activation.  Adds (or writes)
-    the gradient of x0 into gx0.  Returns the parameter gradients in edge_net_tensors order."""
+    the gradient of x0 into gx0.  Returns the parameter gradients in edge_net_tensors order.  _03 (sv.e3 set): the gradient
+    of e3 is ADDED to ge3."""
     dev, N, P, B = gZG2.device, cfg.N, cfg.P, cfg.B
+    e3 = sv.e3
     L = len(chans)
     f = T[16 * L:]
     G = [None] * len(T)
@@ -191,6 +218,9 @@ def edge_backward(cfg, sv, AC, flags, chans, offs, T, gS, gZG2, gx0, gx0_accumul
             G[b + 14], G[b + 15] = wg(GY, s.Hmc, True)
             G[b + 12], G[b + 13] = wg(GHm, s.xcat, True)
             G[b + 5] = slabs.colsum_leaf(GV)
+            if e3 is not None:
+                G[b + 4] = _edge_v_wgrad_cond(s.x, e3, gXV, C, F)
+        if node and e3 is None:
             gWv = _empty(C * F, 16, device=dev)
             # x W_c with W_c stored [in, out]: gW_c = x^T g(xW_c) -- the C channels share x, and their g(xW_c) are adjacent column
             # blocks of gXV: ONE product x^T gXV [F, 16 C] whose column block c is channel c's gradient (the slab reduction
@@ -210,32 +240,54 @@ def edge_backward(cfg, sv, AC, flags, chans, offs, T, gS, gZG2, gx0, gx0_accumul
             wg(gQK[:, 32 * g:32 * g + 32], s.H[:, 32 * g:32 * g + 32], True, out_w=gW1[32 * g:32 * g + 32],
                out_b=gb1[32 * g:32 * g + 32])
         G[b + 2], G[b + 3] = gW1, gb1
-        G[b], G[b + 1] = wg(gH, s.x, True)
+        if e3 is None:
+            G[b], G[b + 1] = wg(gH, s.x, True)
+        else:           # [2C*32, F + F3] (nn.Linear layout): column blocks x^T-side and e3^T-side
+            G[b] = _empty(W2, F + e3.size(1), device=dev)
+            G[b + 1] = slabs.weight_grad_blocks(gH, s.x, True, [(0, F, G[b], 0)])
+            slabs.weight_grad_blocks(gH, e3, False, [(0, e3.size(1), G[b], F)])
         # gradient of the layer input x
         if l > 0:
             gx = _empty(N, 16, device=dev)
-            hip.gemm_ex(gH, t[0], gx, b_kmajor=True)
+            hip.gemm_ex(gH, t[0], gx, b_kmajor=True, N=F)
             dst, acc = gx, True
         else:
-            hip.gemm_ex(gH, t[0], gx0, b_kmajor=True, accumulate=gx0_accumulate)
+            hip.gemm_ex(gH, t[0], gx0, b_kmajor=True, accumulate=gx0_accumulate, N=F)
             dst, acc = gx0, True
         if node:
-            hip.gemm_ex(gXV, t[4], dst, accumulate=acc, N=F, K=16 * C, b_kblk=(16, F * 16, 16))
+            FW = F if e3 is None else F + e3.size(1)
+            hip.gemm_ex(gXV, t[4], dst, accumulate=acc, N=F, K=16 * C, b_kblk=(16, FW * 16, 16))
+        if e3 is not None:          # the e3 side of the q/k and v products: into the gradient of E3
+            F3 = e3.size(1)
+            hip.gemm_ex(gH, t[0][:, F:], ge3, b_kmajor=True, accumulate=True, N=F3)
+            if node:
+                hip.gemm_ex(gXV, t[4][F:], ge3, accumulate=True, N=F3, K=16 * C, b_kblk=(16, (F + F3) * 16, 16))
         g_xnext = dst if l > 0 else None
     return G, gAC
 
 
 # ------------------------------------------------------------------------------------------------ node network
-def node_forward(cfg, XC, F, AC, T):
-    """XC [N, F+64] with x in columns 0..F-1; fills columns F.. with the GCN outputs and runs the final MLP."""
+def node_forward(cfg, XC, F, AC, T, e3=None):
+    """XC [N, F+64] with x in columns 0..F-1; fills columns F.. with the GCN outputs and runs the final MLP.  e3 [N, F3]
+    (_03): GCN layer l reads cat(x_l, e3); W_0 is [F + F3, 16], W_1..3 are [16 + F3, 16] each."""
     dev, N, B = XC.device, cfg.N, cfg.B
-    sv = types.SimpleNamespace()
+    sv = types.SimpleNamespace(e3=e3)
     X = XC[:, :F]
     sv.XW0 = _empty(N, 16, device=dev)
-    hip.gemm_ex(X, T[0], sv.XW0, b_kmajor=True, N=16, K=F)
     ld = XC.stride(0)
-    _lib.call("msde_dense_node_gcn_fwd", _p(sv.XW0), _p(AC), _p(cfg.mol_ptr), _p(cfg.pair_ptr), _p(T[1]), _p(T[2]), B, cfg.n_max,
-              ctypes.c_void_p(XC.data_ptr() + 4 * F), ld, hip._stream())
+    if e3 is None:
+        hip.gemm_ex(X, T[0], sv.XW0, b_kmajor=True, N=16, K=F)
+        _lib.call("msde_dense_node_gcn_fwd", _p(sv.XW0), _p(AC), _p(cfg.mol_ptr), _p(cfg.pair_ptr), _p(T[1]), _p(T[2]), B,
+                  cfg.n_max, ctypes.c_void_p(XC.data_ptr() + 4 * F), ld, hip._stream())
+    else:
+        F3 = e3.size(1)
+        ws = (16 + F3) * 16
+        hip.gemm_ex(X, T[0], sv.XW0, b_kmajor=True, N=16, K=F, A2=e3, B2=T[0][F:], K2=F3)
+        # PE [N, 48] = e3 [W_E,1 | W_E,2 | W_E,3]: one grouped product over the e3 rows of the three stacked weights
+        sv.PE = _empty(N, 48, device=dev)
+        hip.gemm_ex(e3, T[1][16:], sv.PE, b_kmajor=True, groups=3, group_strides=dict(b=ws, c=16), N=16, K=F3)
+        _lib.call("msde_dense_node_gcn_fwd_ex", _p(sv.XW0), _p(AC), _p(cfg.mol_ptr), _p(cfg.pair_ptr), _p(T[1]), ws, _p(T[2]),
+                  _p(sv.PE), 48, B, cfg.n_max, ctypes.c_void_p(XC.data_ptr() + 4 * F), ld, hip._stream())
     w1, w2, nout = T[3].size(0), T[5].size(0), T[7].size(0)
     sv.Z1, sv.F1, sv.Z2, sv.F2 = (_empty(N, w, device=dev) for w in (w1, w1, w2, w2))
     sv.OUT = _empty(N, XP_LD, device=dev)
@@ -289,6 +341,9 @@ def node_backward(cfg, sv, XC, F, AC, T, gOUT):
     hip.gemm_ex(gZ1, T[3], gXC, b_kmajor=True)
     GP, MM = _empty(N, 64, device=dev), _empty(N, 64, device=dev)
     ld = XC.stride(0)
+    e3 = sv.e3
+    if e3 is not None:
+        return _node_backward_cond(cfg, XC, F, AC, T, G, gXC, GP, MM, e3)
     _lib.call("msde_dense_node_gcn_bwd", ctypes.c_void_p(gXC.data_ptr() + 4 * F), gXC.stride(0),
               ctypes.c_void_p(XC.data_ptr() + 4 * F), ld, _p(AC), _p(cfg.mol_ptr), _p(cfg.pair_ptr), _p(T[1]), B, cfg.n_max,
               _p(GP), _p(MM), hip._stream())
@@ -299,6 +354,34 @@ def node_backward(cfg, sv, XC, F, AC, T, gOUT):
     G[1] = gWl
     G[0], _ = wg(XC[:, :F], MM[:, :16], False)
     hip.gemm_ex(MM[:, :16], T[0], gXC[:, :F], accumulate=True, N=F, K=16)       # g x += g(xW_0) W_0^T
+    return G, gXC
+
+
+def _node_backward_cond(cfg, XC, F, AC, T, G, gXC, GP, MM, e3):
+    """The GCN part of node_backward for _03 (layers read cat(x_l, e3)); e3 = XC[:, :F3], whose gradient gXC[:, :F3]
+    receives the e3 side of every layer."""
+    dev, N, B = XC.device, cfg.N, cfg.B
+    wg = slabs.weight_grad
+    F3 = e3.size(1)
+    FW = 16 + F3
+    _lib.call("msde_dense_node_gcn_bwd_ex", ctypes.c_void_p(gXC.data_ptr() + 4 * F), gXC.stride(0),
+              ctypes.c_void_p(XC.data_ptr() + 4 * F), XC.stride(0), _p(AC), _p(cfg.mol_ptr), _p(cfg.pair_ptr), _p(T[1]),
+              FW * 16, B, cfg.n_max, _p(GP), _p(MM), hip._stream())
+    G[2] = slabs.colsum_leaf(GP)
+    gWl = _empty(3 * FW, 16, device=dev)
+    for l in range(1, 4):       # rows 0..15 of W_l: x_l^T MM_l
+        wg(XC[:, F + 16 * (l - 1):F + 16 * l], MM[:, 16 * l:16 * l + 16], False, out_w=gWl[FW * (l - 1):FW * (l - 1) + 16])
+    # rows 16.. of W_1..3: e3^T [MM_1 | MM_2 | MM_3] as ONE product whose column blocks are the three layers' gradients
+    slabs.weight_grad_blocks(e3, MM[:, 16:64], False, [(16 * (l - 1), 16, gWl[FW * (l - 1) + 16:FW * l], 0) for l in range(1, 4)])
+    G[1] = gWl
+    gW0 = _empty(F + F3, 16, device=dev)
+    wg(XC[:, :F], MM[:, :16], False, out_w=gW0[:F])
+    wg(e3, MM[:, :16], False, out_w=gW0[F:])
+    G[0] = gW0
+    hip.gemm_ex(MM[:, :16], T[0], gXC[:, :F], accumulate=True, N=F, K=16)       # g x += g(xW_0) W_0^T (x rows of W_0)
+    ge3 = gXC[:, :F3]
+    hip.gemm_ex(MM[:, :16], T[0][F:], ge3, accumulate=True, N=F3, K=16)          # ... and its e3 rows
+    hip.gemm_ex(MM[:, 16:64], T[1][16:], ge3, accumulate=True, N=F3, K=48, b_kblk=(16, FW * 16, 16))   # layers 1..3
     return G, gXC
 
 
@@ -337,8 +420,9 @@ class _DenseHeadLosses(torch.autograd.Function):
             hip.gemm_ex(h3, W3, XC[:, :F], bias=b3, bias2=bX)
             hip.gemm_ex(px[:, :cfg.ncls], WX, XC[:, :F], accumulate=True)
         chans, offs = cfg.chans, cfg.offs
-        se = edge_forward(cfg, XC[:, :FX], AC, flags, chans, offs, TE)
-        sn = node_forward(cfg, XC, FX, AC, TN)
+        e3 = XC[:, :F] if getattr(cfg, "cond", False) else None        # _03: E3 = embedding_3D(h) beside every layer's input
+        se = edge_forward(cfg, XC[:, :FX], AC, flags, chans, offs, TE, e3=e3)
+        sn = node_forward(cfg, XC, FX, AC, TN, e3=e3)
         f2W, f2b = TE[-2], TE[-1]
         res_adj, res_x = _empty(P, device=dev), _empty(N, XP_LD, device=dev)
         part, out = _empty(B * 4, 2, device=dev), _empty(2, device=dev)      # MSDE_DENSE_LOSS_SPLITS partials per molecule
@@ -371,7 +455,7 @@ class _DenseHeadLosses(torch.autograd.Function):
         concat = bool(getattr(cfg, "concat", False))
         FX = 2 * F if concat else F
         GN, gXC = node_backward(cfg, sn, XC, FX, AC, TN, gOUT)
-        GE, _ = edge_backward(cfg, se, AC, flags, cfg.chans, cfg.offs, TE, gS, gZG2, gXC[:, :FX], True)
+        GE, _ = edge_backward(cfg, se, AC, flags, cfg.chans, cfg.offs, TE, gS, gZG2, gXC[:, :FX], True, ge3=gXC[:, :F])
         gX = gXC[:, :F]                                   # gradient of embedding_3D's output
         gXx = gXC[:, F:FX] if concat else gX              # ... of embedding_X's (the same tensor when they were added)
         gW3, gb3 = slabs.weight_grad(gX, h3, True)
@@ -459,6 +543,10 @@ class ScoreEval:
     layer; its Linear(F2, 1) is folded into the consumer) and OUT [N, XP_LD] (the node network's output)."""
 
     def __init__(self, model, cfg, h3, flags):
+        if getattr(model, "COND_3D", False):
+            # the arithmetic below is the base model's (x = E3 + embedding_X(x), score networks on x alone)
+            raise NotImplementedError(f"{type(model).__name__}: its score networks read embedding_3D(h) beside every layer's "
+                                      "input; the reference has no sampler for it and ScoreEval evaluates the base model only")
         dev = h3.device
         N, P = cfg.N, cfg.P
         F = h3.size(1)

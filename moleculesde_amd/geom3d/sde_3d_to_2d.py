@@ -62,23 +62,25 @@ def _norm_adj(adj):
 
 
 class EdgeLayer(nn.Module):
-    """Parameters of one EdgeLayer (conv='MLP'); evaluated in a stacked fashion by EdgeNetwork_dense."""
+    """Parameters of one EdgeLayer (conv='MLP'); evaluated in a stacked fashion by EdgeNetwork_dense.  node_3D_dim > 0:
+    EdgeLayer_03 (edge_network_dense.py:131-150), whose func_q / func_k / func_v read cat(x, E3) -- in_dim + node_3D_dim inputs."""
 
-    def __init__(self, in_dim, attn_dim, out_dim, num_heads, conv):
+    def __init__(self, in_dim, attn_dim, out_dim, num_heads, conv, node_3D_dim=0):
         super().__init__()
         if conv != "MLP":
             raise NotImplementedError("conv='GCN' is never selected on the MoleculeSDE path")
         self.num_heads, self.attn_dim, self.out_dim = num_heads, attn_dim, out_dim
-        self.func_q = _nn.MultiLayerPerceptron(in_dim, [2 * attn_dim, 2 * attn_dim], activation="tanh")
-        self.func_k = _nn.MultiLayerPerceptron(in_dim, [2 * attn_dim, 2 * attn_dim], activation="tanh")
-        self.func_v = NodeNetwork_dense(in_dim, out_dim)
+        self.func_q = _nn.MultiLayerPerceptron(in_dim + node_3D_dim, [2 * attn_dim, 2 * attn_dim], activation="tanh")
+        self.func_k = _nn.MultiLayerPerceptron(in_dim + node_3D_dim, [2 * attn_dim, 2 * attn_dim], activation="tanh")
+        self.func_v = NodeNetwork_dense(in_dim + node_3D_dim, out_dim)
 
 
 class EdgeNetwork_dense(nn.Module):
-    def __init__(self, num_linears, conv_input_dim, attn_dim, conv_output_dim, input_dim, output_dim, num_heads, conv):
+    def __init__(self, num_linears, conv_input_dim, attn_dim, conv_output_dim, input_dim, output_dim, num_heads, conv,
+                 node_3D_dim=0):
         super().__init__()
         self.attn_dim, self.num_heads = attn_dim, num_heads
-        self.attn = nn.ModuleList([EdgeLayer(conv_input_dim, attn_dim, conv_output_dim, num_heads, conv)
+        self.attn = nn.ModuleList([EdgeLayer(conv_input_dim, attn_dim, conv_output_dim, num_heads, conv, node_3D_dim)
                                    for _ in range(input_dim)])
         self.hidden_dim = 2 * max(input_dim, output_dim)
         self.mlp = _nn.MultiLayerPerceptron(2 * input_dim, [self.hidden_dim] * (num_linears - 1) + [output_dim],
@@ -109,10 +111,14 @@ class EdgeNetwork_dense(nn.Module):
         b1 = torch.stack([m.layers[1].bias for m in mods]).unsqueeze(1)
         return torch.baddbmm(b1, h, W1.transpose(1, 2))                     # last layer: no activation
 
-    def forward(self, x, adj, flags):
-        """x [B,N,F], adj [B,C,N,N] -> x_out [B,N,F_o], adj_out [B,C_o,N,N] (:105-128)."""
+    def forward(self, x, adj, flags, e3=None):
+        """x [B,N,F], adj [B,C,N,N] -> x_out [B,N,F_o], adj_out [B,C_o,N,N] (:105-128).  e3 [B,N,F3] (EdgeNetwork_dense_03,
+        :189-226): every q / k / v product reads cat(x, e3)."""
         B, N, Fd = x.shape
         C = len(self.attn)
+        if e3 is not None:
+            x = torch.cat([x, e3], -1)
+            Fd = x.size(-1)
         x2 = x.reshape(B * N, Fd)
         Q = self._stacked_mlp(x2, "func_q")                                 # [C, BN, 2a]
         K = self._stacked_mlp(x2, "func_k")
@@ -157,6 +163,9 @@ class EdgeScoreNetwork_dense(nn.Module):
         self.final = _nn.MultiLayerPerceptron(self.fdim, [2 * self.fdim, 2 * self.fdim, 1], activation="silu")
 
     def forward(self, x, adj, flags):
+        return self._forward(x, adj, flags, None)
+
+    def _forward(self, x, adj, flags, e3):
         chans = [adj]
         a = adj
         for _ in range(self.c_init - 1):                                    # pow_tensor (:28-37)
@@ -165,7 +174,7 @@ class EdgeScoreNetwork_dense(nn.Module):
         adjc = torch.stack(chans, dim=1)
         adj_list = [adjc]
         for layer in self.layers:
-            x, adjc = layer(x, adjc, flags)
+            x, adjc = layer(x, adjc, flags, e3)
             adj_list.append(adjc)
         adjs = torch.cat(adj_list, dim=1).permute(0, 2, 3, 1)               # [B, N, N, fdim]
         B, N = adjs.shape[:2]
@@ -175,10 +184,10 @@ class EdgeScoreNetwork_dense(nn.Module):
 
 
 class NodeScoreNetwork_dense(nn.Module):
-    def __init__(self, nfeat, depth, nhid, nout):
+    def __init__(self, nfeat, depth, nhid, nout, node_3D_dim=0):
         super().__init__()
         self.nfeat, self.depth, self.nhid, self.nout = nfeat, depth, nhid, nout
-        self.layers = nn.ModuleList([NodeNetwork_dense(nfeat if l == 0 else nhid, nhid) for l in range(depth)])
+        self.layers = nn.ModuleList([NodeNetwork_dense((nfeat if l == 0 else nhid) + node_3D_dim, nhid) for l in range(depth)])
         self.fdim = nfeat + depth * nhid
         self.final = _nn.MultiLayerPerceptron(self.fdim, [2 * self.fdim, 2 * self.fdim, nout], activation="silu")
 
@@ -186,19 +195,58 @@ class NodeScoreNetwork_dense(nn.Module):
         return [[l.weight for l in self.layers[1:]], [l.bias for l in self.layers]]
 
     def forward(self, x, adj, flags):
+        return self._forward(x, adj, flags, None)
+
+    def _forward(self, x, adj, flags, e3):
         B, N, _ = x.shape
         an = _norm_adj(adj)
         x_list = [x]
         for layer in self.layers:
-            x = torch.tanh(torch.matmul(an, torch.matmul(x, layer.weight)) + layer.bias)
+            xi = x if e3 is None else torch.cat([x, e3], -1)                  # NodeNetwork_dense_03 (node_network_dense.py:129)
+            x = torch.tanh(torch.matmul(an, torch.matmul(xi, layer.weight)) + layer.bias)
             x_list.append(x)
         xs = torch.cat(x_list, dim=-1).reshape(B * N, self.fdim)
         out = self.final(xs).view(B, N, -1)                                  # 364 -> 728 -> 728 -> 119 GEMM chain
         return mask_x(out, flags)
 
 
+class EdgeScoreNetwork_dense_03(EdgeScoreNetwork_dense):
+    """invariant_scorenetwork_dense.py:134-178: every EdgeLayer_03 reads cat(x, E3) with E3 = node_3D_repr, dim3D // 2 wide
+    (dim3D is the width of x, the concatenated embeddings).  forward(x, adj, node_3D_repr, flags)."""
+
+    def __init__(self, dim3D, nhid, num_layers, num_linears, c_init, c_hid, c_final, adim, num_heads, conv):
+        nn.Module.__init__(self)
+        self.c_init, self.num_layers = c_init, num_layers
+        self.layers = nn.ModuleList()
+        e = dim3D // 2
+        for l in range(num_layers):
+            if l == 0:
+                self.layers.append(EdgeNetwork_dense(num_linears, dim3D, nhid, nhid, c_init, c_hid, num_heads, conv, e))
+            elif l == num_layers - 1:
+                self.layers.append(EdgeNetwork_dense(num_linears, nhid, adim, nhid, c_hid, c_final, num_heads, conv, e))
+            else:
+                self.layers.append(EdgeNetwork_dense(num_linears, nhid, adim, nhid, c_hid, c_hid, num_heads, conv, e))
+        self.fdim = c_hid * (num_layers - 1) + c_final + c_init
+        self.final = _nn.MultiLayerPerceptron(self.fdim, [2 * self.fdim, 2 * self.fdim, 1], activation="silu")
+
+    def forward(self, x, adj, node_3D_repr, flags):
+        return self._forward(x, adj, flags, node_3D_repr)
+
+
+class NodeScoreNetwork_dense_03(NodeScoreNetwork_dense):
+    """invariant_scorenetwork_dense.py:181-224: GCN layer l reads cat(x_l, E3), nfeat + nfeat // 2 inputs for layer 0 and
+    nhid + nfeat // 2 after it; the final MLP is NodeScoreNetwork_dense's.  forward(x, adj, node_3D_repr, flags)."""
+
+    def __init__(self, nfeat, depth, nhid, nout):
+        super().__init__(nfeat, depth, nhid, nout, node_3D_dim=nfeat // 2)
+
+    def forward(self, x, adj, node_3D_repr, flags):
+        return self._forward(x, adj, flags, node_3D_repr)
+
+
 class SDEModel3Dto2D_node_adj_dense(nn.Module):
     CONCAT_EMBEDDINGS = False     # _02 (below): the two embeddings are concatenated instead of added
+    COND_3D = False               # _03 (below): the score networks also read embedding_3D(h) beside every layer's input
 
     def __init__(self, dim3D, nhid, num_layers, num_linears, c_hid, c_final, adim, emb_dim, beta_min, beta_max,
                  num_diffusion_timesteps, c_init=1, num_heads=4, conv="MLP", noise_mode="discrete", SDE_type="VE",
@@ -220,11 +268,12 @@ class SDEModel3Dto2D_node_adj_dense(nn.Module):
         self.embedding_X = _nn.Linear(num_class_X if noise_on_one_hot else 1, dim3D)
         self.embedding_3D = _nn.Linear(dim3D, dim3D)
         net_in = 2 * dim3D if self.CONCAT_EMBEDDINGS else dim3D
-        self.edge_score_network = EdgeScoreNetwork_dense(dim3D=net_in, nhid=nhid, num_layers=num_layers,
-                                                         num_linears=num_linears, c_init=c_init, c_hid=c_hid,
-                                                         c_final=c_final, adim=adim, num_heads=4, conv=conv)
-        self.node_score_network = NodeScoreNetwork_dense(nfeat=net_in, depth=num_layers, nhid=nhid,
-                                                         nout=num_class_X if noise_on_one_hot else 1)
+        edge_cls, node_cls = ((EdgeScoreNetwork_dense_03, NodeScoreNetwork_dense_03) if self.COND_3D else
+                              (EdgeScoreNetwork_dense, NodeScoreNetwork_dense))
+        self.edge_score_network = edge_cls(dim3D=net_in, nhid=nhid, num_layers=num_layers, num_linears=num_linears,
+                                           c_init=c_init, c_hid=c_hid, c_final=c_final, adim=adim, num_heads=4, conv=conv)
+        self.node_score_network = node_cls(nfeat=net_in, depth=num_layers, nhid=nhid,
+                                           nout=num_class_X if noise_on_one_hot else 1)
         self.noise = _nn.DeviceNoise()
 
     def get_score_fn(self, sde, model, train=True, continuous=True):
@@ -257,6 +306,7 @@ class SDEModel3Dto2D_node_adj_dense(nn.Module):
             dn._fused_cfg = cfg
         cfg.sde_vp = 1 if self.SDE_type == "VP" else 0
         cfg.concat = bool(self.CONCAT_EMBEDDINGS)          # _02: embeddings concatenated (:326), 2 * dim3D-wide score networks
+        cfg.cond = bool(self.COND_3D)                      # _03: every score-network layer also reads embedding_3D(h) (:503-506)
         cfg.p0, cfg.p1 = float(self.beta_min), float(self.beta_max)
         cfg.draws = cfg.t_in = cfg.noise_adj = cfg.noise_x = None
         cfg.nm_pad, cfg.seed, cfg.seed_dev = Nm, 0, None
@@ -327,13 +377,20 @@ class SDEModel3Dto2D_node_adj_dense(nn.Module):
         z_x = mask_x(self.noise.randn_like(x0), flags)
         mean_x, std_x = self.sde_x.marGINal_prob(x0, t)
         perturbed_x = mask_x(mean_x + std_x[:, None, None] * z_x, flags)
+        e3 = self.embedding_3D(h3)
         if self.CONCAT_EMBEDDINGS:
-            perturbed_x = torch.cat([self.embedding_3D(h3), self.embedding_X(perturbed_x)], -1)   # _02 (:326)
+            perturbed_x = torch.cat([e3, self.embedding_X(perturbed_x)], -1)   # _02 (:326), _03 (:505)
         else:
-            perturbed_x = self.embedding_3D(h3) + self.embedding_X(perturbed_x)   # (:156)
+            perturbed_x = e3 + self.embedding_X(perturbed_x)   # (:156)
 
-        score_adj = -self.edge_score_network(perturbed_x, perturbed_adj, flags) / std_adj[:, None, None]   # (:86-94)
-        score_x = -self.node_score_network(perturbed_x, perturbed_adj, flags) / std_x[:, None, None]
+        if self.COND_3D:                                                     # _03: score_fn(x, adj, node_3D_repr, flags, t) (:506-507)
+            net_adj = self.edge_score_network(perturbed_x, perturbed_adj, e3, flags)
+            net_x = self.node_score_network(perturbed_x, perturbed_adj, e3, flags)
+        else:
+            net_adj = self.edge_score_network(perturbed_x, perturbed_adj, flags)
+            net_x = self.node_score_network(perturbed_x, perturbed_adj, flags)
+        score_adj = -net_adj / std_adj[:, None, None]                        # (:86-94)
+        score_x = -net_x / std_x[:, None, None]
 
         losses_x = torch.square(score_x + z_x)
         losses_adj = torch.square(score_adj + z_adj)
@@ -357,10 +414,35 @@ class SDEModel3Dto2D_node_adj_dense_02(SDEModel3Dto2D_node_adj_dense):
     CONCAT_EMBEDDINGS = True
 
 
+class SDEModel3Dto2D_node_adj_dense_03(SDEModel3Dto2D_node_adj_dense):
+    """SDE_model_3D_to_2D_node_adj_dense.py:352-521: _02's concatenated input x = cat(E3, embedding_X(x)) (:505), and every
+    GCN / MLP input of both score networks is cat(x_l, E3) with E3 = embedding_3D(h) (EdgeScoreNetwork_dense_03,
+    NodeScoreNetwork_dense_03).  Same state_dict keys as _02; only the shapes of those input layers differ.  On the fused
+    head (geom3d/dense_head.py) every such product is x_l W_x + E3 W_E in the launch that exists for x_l W alone.  Not a
+    subclass of _02: nothing that accepts _02 may take this model for it."""
+    CONCAT_EMBEDDINGS = True
+    COND_3D = True
+
+    def get_score_fn(self, sde, model, train=True, continuous=True):
+        """(:394-428) score_fn(x, adj, node_3D_repr, flags, t) = -model(x, adj, node_3D_repr, flags) / std(t)."""
+        if not train:
+            model.eval()
+        if not isinstance(sde, (VESDE, VPSDE)):
+            raise NotImplementedError(f"SDE class {sde.__class__.__name__} not supported.")
+
+        def score_fn(x, adj, node_3D_repr, flags, t):
+            if not continuous:
+                raise NotImplementedError("Discrete not supported")
+            std = sde.marGINal_prob(torch.zeros_like(adj), t)[1]
+            return -model(x, adj, node_3D_repr, flags) / std[:, None, None]
+        return score_fn
+
+
 def build_from_args(args, node_class=119):
-    """pretrain_MoleculeSDE.py:276-315 (SDEModel3Dto2D_node_adj_dense branches)."""
+    """pretrain_MoleculeSDE.py:276-330 (SDEModel3Dto2D_node_adj_dense branches)."""
     classes = {"SDEModel3Dto2D_node_adj_dense": SDEModel3Dto2D_node_adj_dense,
-               "SDEModel3Dto2D_node_adj_dense_02": SDEModel3Dto2D_node_adj_dense_02}
+               "SDEModel3Dto2D_node_adj_dense_02": SDEModel3Dto2D_node_adj_dense_02,
+               "SDEModel3Dto2D_node_adj_dense_03": SDEModel3Dto2D_node_adj_dense_03}
     if args.SDE_3Dto2D_model not in classes:
         raise NotImplementedError(args.SDE_3Dto2D_model)
     ranges = {"VE": ("VE", 0.1, 1.0), "VP": ("VP", 0.2, 1.0), "VE02": ("VE", 0.1, 10.0), "VP02": ("VP", 0.1, 30.0),

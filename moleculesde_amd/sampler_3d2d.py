@@ -18,7 +18,7 @@ import torch
 from . import _lib, hip as _hip, plan as _plan, slabs
 from .geom3d import dense_head as _dh
 from .geom3d.sde import VPSDE
-from .geom3d.sde_3d_to_2d import SDEModel3Dto2D_node_adj_dense_02, mask_adjs, mask_x
+from .geom3d.sde_3d_to_2d import SDEModel3Dto2D_node_adj_dense_02, SDEModel3Dto2D_node_adj_dense_03, mask_adjs, mask_x
 
 _p = _hip._p
 
@@ -179,6 +179,12 @@ def _check_model(model, probability_flow):
     if probability_flow:
         raise NotImplementedError("probability_flow=True: the 3D->2D inference script never sets it (its ODE predictor is not "
                                   "built)")
+    if isinstance(model, SDEModel3Dto2D_node_adj_dense_03) or getattr(model, "COND_3D", False):
+        # its score networks read embedding_3D(h) beside every layer's input, score_fn(x, adj, node_3D_repr, flags, t): the
+        # script's sampler passes no conditioning, and the evaluation below is the base model's arithmetic
+        raise NotImplementedError(f"{type(model).__name__}: SDEModel3Dto2D_node_adj_dense_03 conditions every score-network "
+                                  "layer on embedding_3D(h); the reference has no sampler for it (the script's sampler passes "
+                                  "no conditioning)")
     if isinstance(model, SDEModel3Dto2D_node_adj_dense_02):
         raise NotImplementedError("SDEModel3Dto2D_node_adj_dense_02: the script's sampler SUMS embedding_3D and embedding_X "
                                   "(:228,240; SDE_dense.py:88,99), which contradicts _02's concatenated 2*dim3D input")
@@ -333,6 +339,7 @@ def generate_2d_from_3d(molecule_model_3D, SDE_model, data, num_repeat=10, **kw)
     return_latent node representation, sample.  Returns (x, adj, x_mean, adj_mean) padded, [num_repeat, Nm, *]."""
     from .batch import Batch
     from .geom3d.nn import prepare_batch
+    _check_model(SDE_model, kw.get("probability_flow", False))      # before the 3D encoder runs
     dev = next(SDE_model.parameters()).device
     rep_data = prepare_batch(Batch.from_data_list([data] * num_repeat), dev)
     molecule_model_3D.eval()
