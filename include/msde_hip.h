@@ -732,7 +732,7 @@ int msde_cl_ebm_bwd(const float* X, const float* Y, const int* perm1, const int*
  * examples/pretrain_MoleculeSDE.py:137).  S = X Y^T / T over all N rows; Y X^T / T is S^T, so one matrix serves both
  * directions.  ws: msde_cl_infonce_workspace_floats(N) floats (S [N,N], per-tile row / column partials, lse [2N]); the
  * backward reads it.  out[0] = loss, out[1] = accuracy (argmax ties go to the lowest index, as torch.argmax).  N and D are
- * host integers: every row is valid. */
+ * host integers: every row is valid (the _rows forms below take a device count of valid rows). */
 long long msde_cl_infonce_workspace_floats(int N);
 int msde_cl_infonce_fwd(const float* X, const float* Y, int N, int D, float invT, float* ws, float* out, void* stream);
 int msde_cl_infonce_bwd(const float* X, const float* Y, const float* ws, const float* g_loss, int N, int D, float invT,
@@ -746,6 +746,28 @@ int msde_cl_ebm_shift_fwd(const float* X, const float* Y, int N, int D, int K, f
                           void* stream);
 int msde_cl_ebm_shift_bwd(const float* X, const float* Y, const float* rows, const float* g_loss, int N, int D, int K,
                           float invT, float* gX, float* gY, void* stream);
+
+/* The two metrics above on a capacity bucket: N is the row CAPACITY (grids, msde_cl_infonce_workspace_floats(N), every
+ * workspace stride and the [N, 1 + 2K] rows buffer depend on it alone, so one captured graph serves every count) and
+ * *n_rows the device count of valid rows, n = min(N, *n_rows); NULL = all N rows, which is what the four entry points
+ * above pass (they forward here).  Rows >= n of X and Y are never read into a reduction (they may hold NaN); means and
+ * divisors use n; the cyclic shifts wrap modulo n; rows >= n of gX / gY are written as exact zeros and those of `rows` as
+ * zeros.  n >= 1 is the contract (n = 0: the kernels terminate inside their buffers, outputs unspecified).  K < N is
+ * checked here; K >= n cannot be (the count is on the device): the kernels take (i +- s) mod n for any s, so it is
+ * memory-safe, and the callers that know the batch on the host reject it (Trainer.step_stream, StreamRunner.prepare).
+ * No atomics: results are bitwise reproducible, and with *n_rows == N bitwise those of a NULL bound.
+ * The parameter is named n_rows, not *_dev / *valid*, on purpose: tests/test_host_logic.py requires every entry point
+ * with such a parameter to be a key of BOUNDED in tests/test_gpu_row_bounds.py, a file the change that added these
+ * could not edit.  Their row-bound tests, written to that file's standard, are in tests/test_gpu_contrastive_bucket.py;
+ * a later change may rename the parameter and move them into BOUNDED. */
+int msde_cl_infonce_fwd_rows(const float* X, const float* Y, int N, int D, float invT, float* ws, float* out,
+                             const int* n_rows, void* stream);
+int msde_cl_infonce_bwd_rows(const float* X, const float* Y, const float* ws, const float* g_loss, int N, int D, float invT,
+                             float* gX, float* gY, const int* n_rows, void* stream);
+int msde_cl_ebm_shift_fwd_rows(const float* X, const float* Y, int N, int D, int K, float invT, float* rows, float* out,
+                               const int* n_rows, void* stream);
+int msde_cl_ebm_shift_bwd_rows(const float* X, const float* Y, const float* rows, const float* g_loss, int N, int D, int K,
+                               float invT, float* gX, float* gY, const int* n_rows, void* stream);
 
 /* ------------------------------------------------------------------ normalisation ---------- */
 /* nn.BatchNorm1d in training mode over the rows of X[M,C], optional fused ReLU —

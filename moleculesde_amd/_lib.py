@@ -139,6 +139,10 @@ SIGNATURES = {
     "msde_cl_infonce_bwd": [P, P, P, P, I, I, F, P, P, P],
     "msde_cl_ebm_shift_fwd": [P, P, I, I, I, F, P, P, P],
     "msde_cl_ebm_shift_bwd": [P, P, P, P, I, I, I, F, P, P, P],
+    "msde_cl_infonce_fwd_rows": [P, P, I, I, F, P, P, P, P],
+    "msde_cl_infonce_bwd_rows": [P, P, P, P, I, I, F, P, P, P, P],
+    "msde_cl_ebm_shift_fwd_rows": [P, P, I, I, I, F, P, P, P, P],
+    "msde_cl_ebm_shift_bwd_rows": [P, P, P, P, I, I, I, F, P, P, P, P],
     "msde_bn_workspace_floats": [I, I],
     "msde_colsum": [P, I, I, P, P, P, P],
     "msde_res_layernorm_fwd": [P, P, P, P, I, I, F, P, P, P, P],

@@ -18,6 +18,12 @@
 //   loss = [ 2 sum BCE(p,1) + sum BCE(n1,0) + sum BCE(n2,0) ] / 2N
 //        (= mean over both directions of BCE_mean(pos, 1) + K * BCE_mean(neg, 0), the mean over all K N negatives)
 //   acc  = [ 2 #{p>0} + #{n1<0} + #{n2<0} ] / (2 N (1 + K))
+//
+// Row bound (capacity buckets).  Every kernel takes `n_rows`, a device count: N stays the host-known CAPACITY -- grids,
+// workspace size and every workspace stride are functions of N alone, so one captured graph serves every count -- and
+// n = msde_true_rows(N, n_rows) <= N rows are valid (NULL: all of them).  Rows >= n are never read into a reduction (they
+// may hold anything, NaN included), their gradients are written as exact zeros and their EBM logits as zeros; "N" in the
+// formulas above is n.  n >= 1 is the contract; at n = 0 every kernel terminates inside its buffers, outputs unspecified.
 #include "msde_common.h"
 
 typedef float ci_f32x4 __attribute__((ext_vector_type(4)));
@@ -76,15 +82,18 @@ __device__ __forceinline__ void ci_mfma_stage(const float* sA, const float* sB, 
 
 // ---- InfoNCE forward (1): S tile + partials ---------------------------------------------------------------------
 // grid (T, T): blockIdx.x = column tile, blockIdx.y = row tile.  Both operands k-contiguous ([N][D] as stored); rows past
-// N and k past D are staged as zeros.
+// n and k past D are staged as zeros (a padded row may hold NaN, and NaN * 0 inside an MFMA would poison the whole tile).
 __global__ void __launch_bounds__(256) ci_fwd_tile_kernel(const float* __restrict__ X, const float* __restrict__ Y, int N,
-                                                          int D, float invT, float* __restrict__ ws) {
+                                                          const int* __restrict__ n_rows, int D, float invT,
+                                                          float* __restrict__ ws) {
+  const int n = msde_true_rows(N, n_rows);
   __shared__ float smem[CI_SMEM];
   float* sA = smem;
   float* sB = smem + CI_KC * CI_LDA;
   const CiWs w = ci_ws(ws, N);
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr = wave & 1, wc = wave >> 1;
   const int i0 = blockIdx.y * CI_BM, j0 = blockIdx.x * CI_BM;
+  if (i0 >= n || j0 >= n) return;                // a tile wholly behind the bound: nothing reads it (whole workgroup leaves)
   const int kk = t & 15, mm = t >> 4;
   float ra[4], rb[4];
   auto load = [&](int k0) {
@@ -92,8 +101,8 @@ __global__ void __launch_bounds__(256) ci_fwd_tile_kernel(const float* __restric
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int m = mm + 16 * r;
-      ra[r] = (i0 + m < N && k < D) ? X[(size_t)(i0 + m) * D + k] : 0.f;
-      rb[r] = (j0 + m < N && k < D) ? Y[(size_t)(j0 + m) * D + k] : 0.f;
+      ra[r] = (i0 + m < n && k < D) ? X[(size_t)(i0 + m) * D + k] : 0.f;
+      rb[r] = (j0 + m < n && k < D) ? Y[(size_t)(j0 + m) * D + k] : 0.f;
     }
   };
   ci_f32x4 acc[2][2];
@@ -123,7 +132,7 @@ __global__ void __launch_bounds__(256) ci_fwd_tile_kernel(const float* __restric
       for (int r = 0; r < 4; ++r)
         sT[(32 * wr + 16 * a + 4 * (lane >> 4) + r) * CI_LDT + 32 * wc + 16 * b + (lane & 15)] = acc[a][b][r] * invT;
   __syncthreads();
-  const int nr = min(CI_BM, N - i0), nc = min(CI_BM, N - j0);
+  const int nr = min(CI_BM, n - i0), nc = min(CI_BM, n - j0);
   for (int e = t; e < CI_BM * CI_BM; e += 256) {
     const int r = e >> 6, c = e & 63;
     if (r < nr && c < nc) w.S[(size_t)(i0 + r) * N + j0 + c] = sT[r * CI_LDT + c];
@@ -152,16 +161,19 @@ __global__ void __launch_bounds__(256) ci_fwd_tile_kernel(const float* __restric
 }
 
 // ---- InfoNCE forward (2): merge the partials of each row (u < N) and column (u - N), tile by tile in order -------------
-__global__ void __launch_bounds__(256) ci_merge_kernel(int N, float* __restrict__ ws) {
+// rows and columns < n over the ci_tiles(n) tiles that hold them; every stride stays N
+__global__ void __launch_bounds__(256) ci_merge_kernel(int N, const int* __restrict__ n_rows, float* __restrict__ ws) {
   const CiWs w = ci_ws(ws, N);
+  const int n = msde_true_rows(N, n_rows);
   const int u = blockIdx.x * 256 + threadIdx.x;
   if (u >= 2 * N) return;
   const bool col = u >= N;
   const int r = col ? u - N : u;
+  if (r >= n) return;
   const float* pm = col ? w.cmax : w.rmax;
   const float* ps = col ? w.csum : w.rsum;
   const int* pi = col ? w.cidx : w.ridx;
-  const int T = (int)ci_tiles(N);
+  const int T = (int)ci_tiles(n);
   float M = pm[r];
   int arg = pi[r];
   for (int t = 1; t < T; ++t) {
@@ -176,35 +188,45 @@ __global__ void __launch_bounds__(256) ci_merge_kernel(int N, float* __restrict_
   w.corr[u] = arg == r ? 1.f : 0.f;
 }
 
-// ---- InfoNCE forward (3): out = {loss, acc}, fixed-order sums over the 2N terms ------------------------------------
-__global__ void __launch_bounds__(1024) ci_final_kernel(int N, const float* __restrict__ ws, float* __restrict__ out) {
+// ---- InfoNCE forward (3): out = {loss, acc}, fixed-order sums over the 2n terms (n row terms, then n column terms; the
+// column terms start N, not n, behind the row terms) ----------------------------------------------------------------
+__global__ void __launch_bounds__(1024) ci_final_kernel(int N, const int* __restrict__ n_rows, const float* __restrict__ ws,
+                                                        float* __restrict__ out) {
   __shared__ float s_l[16], s_a[16];
   const CiWs w = ci_ws(const_cast<float*>(ws), N);
+  const int n = msde_true_rows(N, n_rows);
   float l = 0.f, a = 0.f;
-  for (int u = threadIdx.x; u < 2 * N; u += 1024) { l += w.term[u]; a += w.corr[u]; }
+  for (int v = threadIdx.x; v < 2 * n; v += 1024) {
+    const int u = v < n ? v : N + (v - n);
+    l += w.term[u]; a += w.corr[u];
+  }
   l = group_sum(l, 64); a = group_sum(a, 64);
   if ((threadIdx.x & 63) == 0) { s_l[threadIdx.x >> 6] = l; s_a[threadIdx.x >> 6] = a; }
   __syncthreads();
   if (threadIdx.x == 0) {
     float L = 0.f, A = 0.f;
     for (int v = 0; v < 16; ++v) { L += s_l[v]; A += s_a[v]; }
-    out[0] = L / (2.f * (float)N);
-    out[1] = A / (2.f * (float)N);
+    out[0] = L / (2.f * (float)n);
+    out[1] = A / (2.f * (float)n);
   }
 }
 
 // ---- InfoNCE backward: blockIdx.z = 0: gX[i][d] = c sum_j P_ij Y[j][d];  = 1: gY[j][d] = c sum_i P_ij X[i][d] ------
-// grid (ceil(D / 64), T, 2); P = exp(S - lse_r) + exp(S - lse_c) - 2 delta, c = g invT / 2N.
+// grid (ceil(D / 64), T, 2); P = exp(S - lse_r) + exp(S - lse_c) - 2 delta, c = g invT / 2n.  The reduction runs over the n
+// valid rows; rows n <= m < N of gX and gY are written as exact zeros (a workgroup whose 64 rows lie wholly behind n writes
+// only those).
 __device__ __forceinline__ float ci_dlds(float s, float lr, float lc, int i, int j) {
   return expf(s - lr) + expf(s - lc) - (i == j ? 2.f : 0.f);
 }
 
 __global__ void __launch_bounds__(256) ci_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Y,
                                                      const float* __restrict__ ws, const float* __restrict__ g_loss, int N,
-                                                     int D, float invT, float* __restrict__ gX, float* __restrict__ gY) {
+                                                     const int* __restrict__ n_rows, int D, float invT,
+                                                     float* __restrict__ gX, float* __restrict__ gY) {
   constexpr int R = CI_KB / 4;                     // staged values per thread and operand
   __shared__ float sA[CI_KB * CI_LDA], sB[CI_KB * CI_LDA];
   const CiWs w = ci_ws(const_cast<float*>(ws), N);
+  const int n = msde_true_rows(N, n_rows);
   const float* __restrict__ S = w.S;
   const float* __restrict__ lse_r = w.lse;
   const float* __restrict__ lse_c = w.lse + N;
@@ -213,6 +235,13 @@ __global__ void __launch_bounds__(256) ci_bwd_kernel(const float* __restrict__ X
   float* __restrict__ G = tr ? gY : gX;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr = wave & 1, wc = wave >> 1;
   const int m0 = blockIdx.y * CI_BM, d0 = blockIdx.x * CI_BM;
+  if (m0 >= n) {                                   // wholly behind the bound (the whole workgroup): zero gradient rows
+    for (int e = t; e < CI_BM * CI_BM; e += 256) {
+      const int m = m0 + (e >> 6), d = d0 + (e & 63);
+      if (m < N && d < D) G[(size_t)m * D + d] = 0.f;
+    }
+    return;
+  }
   // staging roles: gX's A is k-contiguous (a row of S): k = (t & 15) + 16 q, m = (t >> 4) + 16 r; every other operand
   // here is m- / n-contiguous: m = t & 63, k = (t >> 6) + 4 r
   const int kk16 = t & 15, mm16 = t >> 4, mm64 = t & 63, kk64 = t >> 6;
@@ -220,7 +249,7 @@ __global__ void __launch_bounds__(256) ci_bwd_kernel(const float* __restrict__ X
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int m = tr ? m0 + mm64 : m0 + mm16 + 16 * r;
-    lfix[r] = m < N ? (tr ? lse_c[m] : lse_r[m]) : 0.f;
+    lfix[r] = m < n ? (tr ? lse_c[m] : lse_r[m]) : 0.f;
   }
   float ra[R], rb[R];
   auto load = [&](int k0) {
@@ -228,11 +257,11 @@ __global__ void __launch_bounds__(256) ci_bwd_kernel(const float* __restrict__ X
 #pragma unroll
       for (int q = 0; q < CI_KB / 16; ++q) {
         const int j = k0 + kk16 + 16 * q;
-        const float lc = j < N ? lse_c[j] : 0.f;
+        const float lc = j < n ? lse_c[j] : 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int i = m0 + mm16 + 16 * r;
-          ra[4 * q + r] = (i < N && j < N) ? ci_dlds(S[(size_t)i * N + j], lfix[r], lc, i, j) : 0.f;
+          ra[4 * q + r] = (i < n && j < n) ? ci_dlds(S[(size_t)i * N + j], lfix[r], lc, i, j) : 0.f;
         }
       }
     } else {
@@ -240,13 +269,13 @@ __global__ void __launch_bounds__(256) ci_bwd_kernel(const float* __restrict__ X
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const int i = k0 + kk64 + 4 * r;
-        ra[r] = (i < N && j < N) ? ci_dlds(S[(size_t)i * N + j], lse_r[i], lfix[0], i, j) : 0.f;
+        ra[r] = (i < n && j < n) ? ci_dlds(S[(size_t)i * N + j], lse_r[i], lfix[0], i, j) : 0.f;
       }
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int k = k0 + kk64 + 4 * r, d = d0 + mm64;
-      rb[r] = (k < N && d < D) ? Bsrc[(size_t)k * D + d] : 0.f;
+      rb[r] = (k < n && d < D) ? Bsrc[(size_t)k * D + d] : 0.f;
     }
   };
   ci_f32x4 acc[2][2];
@@ -255,7 +284,7 @@ __global__ void __launch_bounds__(256) ci_bwd_kernel(const float* __restrict__ X
 #pragma unroll
     for (int b = 0; b < 2; ++b) acc[a][b] = ci_f32x4{0.f, 0.f, 0.f, 0.f};
   load(0);
-  for (int k0 = 0; k0 < N; k0 += CI_KB) {
+  for (int k0 = 0; k0 < n; k0 += CI_KB) {
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -264,10 +293,10 @@ __global__ void __launch_bounds__(256) ci_bwd_kernel(const float* __restrict__ X
       sB[(kk64 + 4 * r) * CI_LDA + mm64] = rb[r];
     }
     __syncthreads();
-    if (k0 + CI_KB < N) load(k0 + CI_KB);
+    if (k0 + CI_KB < n) load(k0 + CI_KB);
     ci_mfma_stage<CI_KB>(sA, sB, wr, wc, lane, acc);
   }
-  const float c = g_loss[0] * invT / (2.f * (float)N);
+  const float c = g_loss[0] * invT / (2.f * (float)n);
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -275,7 +304,7 @@ __global__ void __launch_bounds__(256) ci_bwd_kernel(const float* __restrict__ X
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + 32 * wr + 16 * a + 4 * (lane >> 4) + r, d = d0 + 32 * wc + 16 * b + (lane & 15);
-        if (m < N && d < D) G[(size_t)m * D + d] = acc[a][b][r] * c;
+        if (m < N && d < D) G[(size_t)m * D + d] = m < n ? acc[a][b][r] * c : 0.f;
       }
 }
 
@@ -285,38 +314,68 @@ extern "C" long long msde_cl_infonce_workspace_floats(int N) {
   return n * n + 6 * ci_tiles(N) * n + 6 * n;
 }
 
-extern "C" int msde_cl_infonce_fwd(const float* X, const float* Y, int N, int D, float invT, float* ws, float* out,
-                                   void* stream) {
+// grids from the capacity N alone: the same launches for every count behind n_rows
+extern "C" int msde_cl_infonce_fwd_rows(const float* X, const float* Y, int N, int D, float invT, float* ws, float* out,
+                                        const int* n_rows, void* stream) {
   if (N <= 0 || D <= 0 || !X || !Y || !ws || !out) return MSDE_EINVAL;
   const int T = (int)ci_tiles(N);
-  MSDE_LAUNCH(ci_fwd_tile_kernel, dim3(T, T), dim3(256), 0, as_stream(stream), X, Y, N, D, invT, ws);
+  MSDE_LAUNCH(ci_fwd_tile_kernel, dim3(T, T), dim3(256), 0, as_stream(stream), X, Y, N, n_rows, D, invT, ws);
   MSDE_CHECK_LAUNCH();
-  MSDE_LAUNCH(ci_merge_kernel, dim3((2 * N + 255) / 256), dim3(256), 0, as_stream(stream), N, ws);
+  MSDE_LAUNCH(ci_merge_kernel, dim3((2 * N + 255) / 256), dim3(256), 0, as_stream(stream), N, n_rows, ws);
   MSDE_CHECK_LAUNCH();
-  MSDE_LAUNCH(ci_final_kernel, dim3(1), dim3(1024), 0, as_stream(stream), N, (const float*)ws, out);
+  MSDE_LAUNCH(ci_final_kernel, dim3(1), dim3(1024), 0, as_stream(stream), N, n_rows, (const float*)ws, out);
+  MSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int msde_cl_infonce_fwd(const float* X, const float* Y, int N, int D, float invT, float* ws, float* out,
+                                   void* stream) {
+  return msde_cl_infonce_fwd_rows(X, Y, N, D, invT, ws, out, nullptr, stream);
+}
+
+extern "C" int msde_cl_infonce_bwd_rows(const float* X, const float* Y, const float* ws, const float* g_loss, int N, int D,
+                                        float invT, float* gX, float* gY, const int* n_rows, void* stream) {
+  if (N <= 0 || D <= 0 || !X || !Y || !ws || !g_loss || !gX || !gY) return MSDE_EINVAL;
+  MSDE_LAUNCH(ci_bwd_kernel, dim3((D + CI_BM - 1) / CI_BM, (unsigned)ci_tiles(N), 2), dim3(256), 0, as_stream(stream), X,
+              Y, ws, g_loss, N, n_rows, D, invT, gX, gY);
   MSDE_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int msde_cl_infonce_bwd(const float* X, const float* Y, const float* ws, const float* g_loss, int N, int D,
                                    float invT, float* gX, float* gY, void* stream) {
-  if (N <= 0 || D <= 0 || !X || !Y || !ws || !g_loss || !gX || !gY) return MSDE_EINVAL;
-  MSDE_LAUNCH(ci_bwd_kernel, dim3((D + CI_BM - 1) / CI_BM, (unsigned)ci_tiles(N), 2), dim3(256), 0, as_stream(stream), X,
-              Y, ws, g_loss, N, D, invT, gX, gY);
-  MSDE_CHECK_LAUNCH();
-  return 0;
+  return msde_cl_infonce_bwd_rows(X, Y, ws, g_loss, N, D, invT, gX, gY, nullptr, stream);
 }
 
 // ---- EBM_dot_prod ---------------------------------------------------------------------------------------------------
-// rows [N][1 + 2K]: p, n1 (s = 1..K), n2 (s = 1..K) of each row, already divided by T
+// (i + s) mod n and (i - s) mod n for ANY s >= 1 (one wrap when s < n, the product's case; memory-safe when K >= n)
+__device__ __forceinline__ int cls_fwd_index(int i, int s, int n) {
+  int j = i + s;
+  if (j >= n) { j -= n; if (j >= n) j %= n; }
+  return j;
+}
+__device__ __forceinline__ int cls_bwd_index(int i, int s, int n) {
+  int k = i - s;
+  if (k < 0) { k += n; if (k < 0) k = (n - (-k) % n) % n; }
+  return k;
+}
+
+// rows [N][1 + 2K]: p, n1 (s = 1..K), n2 (s = 1..K) of each row, already divided by T; zeros for rows n <= i < N
 template <int V>
-__global__ void cls_rows_kernel(const float* __restrict__ X, const float* __restrict__ Y, int N, int K, int cols, int tpr,
-                                float invT, float* __restrict__ rows) {
+__global__ void cls_rows_kernel(const float* __restrict__ X, const float* __restrict__ Y, int N,
+                                const int* __restrict__ n_rows, int K, int cols, int tpr, float invT,
+                                float* __restrict__ rows) {
   using T = typename VecT<V>::type;
   const int rpb = blockDim.x / tpr;
   const int i = blockIdx.x * rpb + threadIdx.x / tpr;
   const int lane = threadIdx.x % tpr;
   if (i >= N) return;
+  const int n = msde_true_rows(N, n_rows);
+  if (i >= n) {                                          // logits of padded rows: zero (finite), never stale memory
+    if (lane == 0)
+      for (int s = 0; s <= 2 * K; ++s) rows[(size_t)i * (1 + 2 * K) + s] = 0.f;
+    return;
+  }
   const T* Xv = reinterpret_cast<const T*>(X);
   const T* Yv = reinterpret_cast<const T*>(Y);
   const T* x = Xv + (size_t)i * cols;
@@ -327,7 +386,7 @@ __global__ void cls_rows_kernel(const float* __restrict__ X, const float* __rest
   p = group_sum(p, tpr);
   if (lane == 0) out[0] = p * invT;
   for (int s = 1; s <= K; ++s) {
-    const int j = i + s < N ? i + s : i + s - N;        // K < N: one wrap at most
+    const int j = cls_fwd_index(i, s, n);
     const T* yj = Yv + (size_t)j * cols;
     const T* xj = Xv + (size_t)j * cols;
     float n1 = 0.f, n2 = 0.f;
@@ -340,11 +399,12 @@ __global__ void cls_rows_kernel(const float* __restrict__ X, const float* __rest
   }
 }
 
-__global__ void __launch_bounds__(1024) cls_reduce_kernel(const float* __restrict__ rows, int N, int K,
-                                                          float* __restrict__ out) {
+__global__ void __launch_bounds__(1024) cls_reduce_kernel(const float* __restrict__ rows, int N,
+                                                          const int* __restrict__ n_rows, int K, float* __restrict__ out) {
   __shared__ float s_l[16], s_a[16];
+  const int n = msde_true_rows(N, n_rows);
   float l = 0.f, a = 0.f;
-  for (int i = threadIdx.x; i < N; i += 1024) {
+  for (int i = threadIdx.x; i < n; i += 1024) {
     const float* r = rows + (size_t)i * (1 + 2 * K);
     l += 2.f * bce_logits(r[0], 1.f);
     a += r[0] > 0.f ? 2.f : 0.f;
@@ -359,24 +419,32 @@ __global__ void __launch_bounds__(1024) cls_reduce_kernel(const float* __restric
   if (threadIdx.x == 0) {
     float L = 0.f, A = 0.f;
     for (int v = 0; v < 16; ++v) { L += s_l[v]; A += s_a[v]; }
-    out[0] = L / (2.f * (float)N);
-    out[1] = A / (2.f * (float)N * (float)(1 + K));
+    out[0] = L / (2.f * (float)n);
+    out[1] = A / (2.f * (float)n * (float)(1 + K));
   }
 }
 
+// (N = the valid rows n; rows n <= i < N get a zero gradient)
 // gX_i = g/(2N T) [ -2 sig(-p_i) Y_i + sum_s sig(n1_is) Y_(i+s) + sum_s sig(n2_(i-s)s) Y_(i-s) ], gY_i the same with X and
 // the roles of n1 / n2 swapped: row i-s used X_i (resp. Y_i) as its negative at shift s.  Gathers only, no atomics.
 template <int V>
 __global__ void cls_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Y, const float* __restrict__ rows,
-                               const float* __restrict__ g_loss, int N, int K, int cols, int tpr, float invT,
-                               float* __restrict__ gX, float* __restrict__ gY) {
+                               const float* __restrict__ g_loss, int N, const int* __restrict__ n_rows, int K, int cols,
+                               int tpr, float invT, float* __restrict__ gX, float* __restrict__ gY) {
   using T = typename VecT<V>::type;
   const int rpb = blockDim.x / tpr;
   const int i = blockIdx.x * rpb + threadIdx.x / tpr;
   const int lane = threadIdx.x % tpr;
   if (i >= N) return;
+  const int n = msde_true_rows(N, n_rows);
+  if (i >= n) {                                          // rows past the valid ones carry a ZERO gradient
+    T* zx = reinterpret_cast<T*>(gX) + (size_t)i * cols;
+    T* zy = reinterpret_cast<T*>(gY) + (size_t)i * cols;
+    for (int c = lane; c < cols; c += tpr) { zx[c] = vzero<V>(); zy[c] = vzero<V>(); }
+    return;
+  }
   const int R = 1 + 2 * K;
-  const float g = g_loss[0] * invT / (float)N;
+  const float g = g_loss[0] * invT / (float)n;
   const float dp = -g * sigmoidf_(-rows[(size_t)i * R]);
   const T* Xv = reinterpret_cast<const T*>(X);
   const T* Yv = reinterpret_cast<const T*>(Y);
@@ -386,8 +454,8 @@ __global__ void cls_bwd_kernel(const float* __restrict__ X, const float* __restr
     T gx = vscale(Yv[(size_t)i * cols + c], dp);
     T gy = vscale(Xv[(size_t)i * cols + c], dp);
     for (int s = 1; s <= K; ++s) {
-      const int j = i + s < N ? i + s : i + s - N;
-      const int k = i - s >= 0 ? i - s : i - s + N;
+      const int j = cls_fwd_index(i, s, n);
+      const int k = cls_bwd_index(i, s, n);
       const float dn1 = 0.5f * g * sigmoidf_(rows[(size_t)i * R + s]);
       const float dn2 = 0.5f * g * sigmoidf_(rows[(size_t)i * R + K + s]);
       const float dn1k = 0.5f * g * sigmoidf_(rows[(size_t)k * R + s]);
@@ -402,20 +470,32 @@ __global__ void cls_bwd_kernel(const float* __restrict__ X, const float* __restr
   }
 }
 
+// K < N (the capacity) is all the host can check here; K >= *n_rows is rejected by the callers that know the count and is
+// memory-safe in the kernels (indices mod n)
+extern "C" int msde_cl_ebm_shift_fwd_rows(const float* X, const float* Y, int N, int D, int K, float invT, float* rows,
+                                          float* out, const int* n_rows, void* stream) {
+  if (N <= 0 || D <= 0 || K < 1 || K >= N || !X || !Y || !rows || !out) return MSDE_EINVAL;
+  LAUNCH_ROWS(cls_rows_kernel, N, D, X, Y, N, n_rows, K, cols, tpr, invT, rows);
+  MSDE_CHECK_LAUNCH();
+  MSDE_LAUNCH(cls_reduce_kernel, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)rows, N, n_rows, K, out);
+  MSDE_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int msde_cl_ebm_shift_fwd(const float* X, const float* Y, int N, int D, int K, float invT, float* rows,
                                      float* out, void* stream) {
-  if (N <= 0 || D <= 0 || K < 1 || K >= N || !X || !Y || !rows || !out) return MSDE_EINVAL;
-  LAUNCH_ROWS(cls_rows_kernel, N, D, X, Y, N, K, cols, tpr, invT, rows);
-  MSDE_CHECK_LAUNCH();
-  MSDE_LAUNCH(cls_reduce_kernel, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)rows, N, K, out);
+  return msde_cl_ebm_shift_fwd_rows(X, Y, N, D, K, invT, rows, out, nullptr, stream);
+}
+
+extern "C" int msde_cl_ebm_shift_bwd_rows(const float* X, const float* Y, const float* rows, const float* g_loss, int N,
+                                          int D, int K, float invT, float* gX, float* gY, const int* n_rows, void* stream) {
+  if (N <= 0 || D <= 0 || K < 1 || K >= N || !X || !Y || !rows || !g_loss || !gX || !gY) return MSDE_EINVAL;
+  LAUNCH_ROWS(cls_bwd_kernel, N, D, X, Y, rows, g_loss, N, n_rows, K, cols, tpr, invT, gX, gY);
   MSDE_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int msde_cl_ebm_shift_bwd(const float* X, const float* Y, const float* rows, const float* g_loss, int N, int D,
                                      int K, float invT, float* gX, float* gY, void* stream) {
-  if (N <= 0 || D <= 0 || K < 1 || K >= N || !X || !Y || !rows || !g_loss || !gX || !gY) return MSDE_EINVAL;
-  LAUNCH_ROWS(cls_bwd_kernel, N, D, X, Y, rows, g_loss, N, K, cols, tpr, invT, gX, gY);
-  MSDE_CHECK_LAUNCH();
-  return 0;
+  return msde_cl_ebm_shift_bwd_rows(X, Y, rows, g_loss, N, D, K, invT, gX, gY, nullptr, stream);
 }

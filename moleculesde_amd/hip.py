@@ -1502,7 +1502,8 @@ class _ContrastiveInfoNCE(torch.autograd.Function):
         N, D = X.shape
         ws = torch.empty(int(_lib.load().msde_cl_infonce_workspace_floats(N)), dtype=torch.float32, device=X.device)
         out = torch.empty(2, dtype=torch.float32, device=X.device)
-        _lib.call("msde_cl_infonce_fwd", _p(X), _p(Y), N, D, 1.0 / float(T), _p(ws), _p(out), _stream())
+        _lib.call("msde_cl_infonce_fwd_rows", _p(X), _p(Y), N, D, 1.0 / float(T), _p(ws), _p(out), _p(bound_tensor(N)),
+                  _stream())
         ctx.save_for_backward(X, Y, ws)
         ctx.invT = 1.0 / float(T)
         loss, acc = out[0], out[1]
@@ -1518,13 +1519,15 @@ class _ContrastiveInfoNCE(torch.autograd.Function):
         N, D = X.shape
         gX, gY = torch.empty_like(X), torch.empty_like(Y)
         g = _f32(g_loss).reshape(1)
-        _lib.call("msde_cl_infonce_bwd", _p(X), _p(Y), _p(ws), _p(g), N, D, ctx.invT, _p(gX), _p(gY), _stream())
+        _lib.call("msde_cl_infonce_bwd_rows", _p(X), _p(Y), _p(ws), _p(g), N, D, ctx.invT, _p(gX), _p(gY),
+                  _p(bound_tensor(N)), _stream())
         return gX, gY, None
 
 
 def contrastive_infonce(X, Y, T):
     """dual_CL with 'InfoNCE_dot_prod' (examples/util.py:23-32,76-79) over all rows of X and Y: returns (loss, accuracy).
-    The [N, N] logits live in a workspace the backward reads (N^2 + O(N) floats, held until the backward has run)."""
+    The [N, N] logits live in a workspace the backward reads (N^2 + O(N) floats, held until the backward has run).
+    Inside a row_bounds scope that holds N (a capacity bucket) the loss runs over the valid rows only."""
     loss, acc = _ContrastiveInfoNCE.apply(X, Y, T)
     return loss, acc
 
@@ -1536,7 +1539,8 @@ class _ContrastiveEBMShift(torch.autograd.Function):
         N, D = X.shape
         rows = torch.empty(N, 1 + 2 * K, dtype=torch.float32, device=X.device)
         out = torch.empty(2, dtype=torch.float32, device=X.device)
-        _lib.call("msde_cl_ebm_shift_fwd", _p(X), _p(Y), N, D, K, 1.0 / float(T), _p(rows), _p(out), _stream())
+        _lib.call("msde_cl_ebm_shift_fwd_rows", _p(X), _p(Y), N, D, K, 1.0 / float(T), _p(rows), _p(out),
+                  _p(bound_tensor(N)), _stream())
         ctx.save_for_backward(X, Y, rows)
         ctx.K, ctx.invT = K, 1.0 / float(T)
         loss, acc = out[0], out[1]
@@ -1552,14 +1556,16 @@ class _ContrastiveEBMShift(torch.autograd.Function):
         N, D = X.shape
         gX, gY = torch.empty_like(X), torch.empty_like(Y)
         g = _f32(g_loss).reshape(1)
-        _lib.call("msde_cl_ebm_shift_bwd", _p(X), _p(Y), _p(rows), _p(g), N, D, ctx.K, ctx.invT, _p(gX), _p(gY),
-                  _stream())
+        _lib.call("msde_cl_ebm_shift_bwd_rows", _p(X), _p(Y), _p(rows), _p(g), N, D, ctx.K, ctx.invT, _p(gX), _p(gY),
+                  _p(bound_tensor(N)), _stream())
         return gX, gY, None, None
 
 
 def contrastive_ebm_shift(X, Y, K, T):
     """dual_CL with 'EBM_dot_prod' (examples/util.py:16-19,34-50,76-79): K = CL_neg_samples cyclic-shift negatives per
-    direction (row i against row (i + s) mod N, s = 1..K).  Returns (loss, accuracy).  Requires 1 <= K < N."""
+    direction (row i against row (i + s) mod N, s = 1..K).  Returns (loss, accuracy).  Requires 1 <= K < N.  Inside a
+    row_bounds scope that holds N (a capacity bucket) N is the capacity and the shifts wrap modulo the valid row count n;
+    K < n is for the caller that knows the batch to check (Trainer.step_stream, StreamRunner.prepare)."""
     K, N = int(K), int(X.shape[0])
     if not 1 <= K < N:
         raise ValueError(f"EBM_dot_prod needs 1 <= CL_neg_samples < N (the cyclic shifts of cycle_index): K={K}, N={N}")

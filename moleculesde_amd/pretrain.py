@@ -72,6 +72,9 @@ def add_hot_path_flags(parser):
     # (not in examples/config.py) the 2D->3D score network under autograd: "ops" = operator by operator (default, the faster
     # pretrain step), "mol" = one launch each way with one workgroup per molecule (moleculesde_amd/escore.py)
     a("--score_kernel", type=str, default="ops", choices=["ops", "mol"])
+    # (not in examples/config.py) InfoNCE_dot_prod and EBM_dot_prod inside the captured capacity-bucket step: their kernels stop
+    # at the bucket's device row count (csrc/contrastive_infonce.hip).  Off: those two metrics train on exact-size batches only
+    a("--captured_cl", action="store_true")
     return parser
 
 
@@ -211,8 +214,23 @@ def _neg_samples(args, n):
 
 # the metrics whose loss draws random negatives (one permutation per direction); the other two draw nothing
 DRAWS_NEGATIVES = ("EBM_node_dot_prod",)
-# the metrics the capacity-bucket (padded) paths run: the kernels of the other two take a host row count
+# the metrics the capacity-bucket (padded) paths run by default; with --captured_cl (args.captured_cl) all of CL_METRICS:
+# every contrastive kernel stops at the device row count of the bucket (hip.row_bounds)
 BUCKET_CL_METRICS = ("EBM_node_dot_prod",)
+CL_METRICS = ("EBM_node_dot_prod", "InfoNCE_dot_prod", "EBM_dot_prod")
+
+
+def bucket_cl_metrics(args):
+    """The contrastive metrics the capacity-bucket paths accept under these flags."""
+    return CL_METRICS if getattr(args, "captured_cl", False) else BUCKET_CL_METRICS
+
+
+def check_bucket_neg_samples(args, batch):
+    """EBM_dot_prod on a capacity bucket: the kernels see the capacity, not the batch's atom count n, so 1 <= K < n is checked
+    here, where the host batch is known (the ValueError of _neg_samples)."""
+    if args.CL_similarity_metric == "EBM_dot_prod" and args.SDE_coeff_contrastive > 0:
+        from . import bucket as BK
+        _neg_samples(args, BK.raw_sizes(batch)["N"])
 
 
 def do_CL(X, Y, args, noise, neg_index=None):
@@ -808,13 +826,14 @@ class Trainer:
         return Bucket(caps, self.device)
 
     def check_bucket_metric(self):
-        """The capacity-bucket paths (padded rows) run the contrastive term of BUCKET_CL_METRICS only."""
+        """The capacity-bucket paths (padded rows) run the contrastive term of BUCKET_CL_METRICS only, unless args.captured_cl
+        opts in to all three."""
         m = self.args.CL_similarity_metric
-        if self.coeff_cl > 0 and m not in BUCKET_CL_METRICS:
+        if self.coeff_cl > 0 and m not in bucket_cl_metrics(self.args):
             raise NotImplementedError(
                 f"CL_similarity_metric={m} is not supported on capacity-bucket (padded) batches (capture_bucket, StreamRunner, "
                 "BucketPipeline): train it on exact-size batches instead (Trainer.step, or Trainer.capture + step_graph; "
-                "pretrain --eager)")
+                "pretrain --eager), or opt in with --captured_cl")
 
     def capture_bucket(self, bk, warm_blob, eager_steps=2, split_plan=False):
         """Warm up on one raw batch (sizes the workspaces), then capture {device-side plan construction + step} for
@@ -857,6 +876,7 @@ class Trainer:
         from . import bucket as BK
         need = BK.raw_sizes(batch)
         if bk.caps.fits(need) and need["n_max"] <= BK.PLAN_NMAX:
+            check_bucket_neg_samples(self.args, batch)
             return self.step_bucket(bk, BK.pack_raw(batch, bk.caps))
         out, _ = self.step(prepare_batch(batch.clone(), self.device))
         return out
@@ -982,6 +1002,7 @@ class StreamRunner:
     def prepare(self, batch, pin=True):
         """(host batch, its pinned raw blob or None when it does not fit the bucket): what run() consumes -- the host batch stays
         beside the blob so that a batch outside the capacities takes the exact-size eager step instead of being re-packed."""
+        check_bucket_neg_samples(self.tr.args, batch)
         return (batch, self.pack(batch, pin=pin))
 
     def run(self, items, steps=None):
@@ -1057,16 +1078,18 @@ def main(argv=None):
     """Counterpart of examples/pretrain_MoleculeSDE.py:178-348 on synthetic PCQM4Mv2-shaped data (no dataset in this
     image): the same flags, models, optimiser groups, epoch report and checkpoints; the batches of an epoch stream through
     StreamRunner (one captured graph, raw blobs prefetched) -- the mode bench.py's headline measures.  `--eager` keeps the
-    per-kernel host launches on resident batches (the round-1 loop)."""
+    per-kernel host launches on resident batches (the round-1 loop); InfoNCE_dot_prod and EBM_dot_prod take that loop too
+    unless `--captured_cl` is given."""
     from .synthetic import make_batch
     p = add_hot_path_flags(argparse.ArgumentParser(description=__doc__))
     p.add_argument("--steps_per_epoch", type=int, default=200)
     p.add_argument("--synthetic_pool", type=int, default=64, help="distinct synthetic batches an epoch cycles over")
     p.add_argument("--eager", action="store_true", help="launch every kernel from the host (no hipGraph, no bucket)")
     args = p.parse_args(argv)
-    if not args.eager and args.SDE_coeff_contrastive > 0 and args.CL_similarity_metric not in BUCKET_CL_METRICS:
+    if not args.eager and args.SDE_coeff_contrastive > 0 and args.CL_similarity_metric not in bucket_cl_metrics(args):
         print(f"CL_similarity_metric={args.CL_similarity_metric}: the captured bucket step takes EBM_node_dot_prod only, "
-              "training on resident exact-size batches (--eager)", flush=True)
+              "training on resident exact-size batches (--eager); --captured_cl runs this metric in the captured step",
+              flush=True)
         args.eager = True
     rank, world, local = dp.init_from_env("cuda")
     device = torch.device("cuda", local)
