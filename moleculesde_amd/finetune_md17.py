@@ -27,8 +27,8 @@ import numpy as np
 import torch
 
 from . import _lib, dd, hip, slabs, wcache
-from .finetune_molnet import CosineAnnealing
-from .finetune_qm9 import StepDecay, checkpoint_dict
+from .capture import CaptureSession, CapturedStep, optimizer_restore, optimizer_snapshot
+from .finetune_common import FineTuner, hip_device, load_state as _load_state, make_scheduler, painn_radius_edges  # noqa: F401
 from .optim import FlatAdam
 
 
@@ -42,12 +42,10 @@ class ForceTrainer:
         self.energy_coeff, self.force_coeff = float(energy_coeff), float(force_coeff)
         self.normalization = normalization
         params = list(model.parameters()) + (list(graph_pred_linear.parameters()) if graph_pred_linear is not None else [])
-        self.device = params[0].device
-        if self.device.type != "cuda":
-            raise RuntimeError("moleculesde_amd.finetune_md17 runs on the HIP device only (no CPU fallback)")
+        self.device = hip_device(params[0], "finetune_md17")
         self.opt = FlatAdam([{"params": params, "lr": lr}], weight_decay=weight_decay)
         self.is_painn = type(model).__name__ == "PaiNN"
-        self._graph = None
+        self._captured = None
 
     # ---- one step, launched from the host ------------------------------------------------------------------------
     def energy_and_force(self, batch, positions, create_graph=True, negate=True):
@@ -94,11 +92,8 @@ class ForceTrainer:
         self.opt.zero_grad()
         # the weight gradients of the whole step (two contributions per Linear: energy path and force path) as ONE grouped
         # launch + ONE slab reduction behind the backward pass (slabs.weight_grad_leaf) instead of ~170 per-layer launches
-        slabs.begin_param_grad_batch(self.opt.params)
-        try:
+        with slabs.param_grad_batch(self.opt.params):
             torch.autograd.backward([energy, dE], [g_e, g_d])
-        finally:
-            slabs.finish_param_grad_batch()
         self.opt.step_from_grads()
         self._refreshed = wcache.refresh_weight_t()    # re-laid-out weight copies (if a layer reads one) follow the update
         return loss.detach()
@@ -122,17 +117,9 @@ class ForceTrainer:
         self._f = force.float().clone()
         for _ in range(eager_steps):
             self._body(batch, self._pos, self._y, self._f)
-        self.opt.new_table_slot()
-        slabs.new_param_grad_slot(self.device)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with slabs.no_gc(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._loss = self._body(batch, self._pos, self._y, self._f)
-        slabs.flush_table_uploads()
-        self.opt.use_eager_slot()
-        slabs.use_eager_param_grad_slot()
-        self._graph = g
-        self._graph_wt_keys = self._refreshed          # the copies the captured refresh launch re-lays-out at every replay
+        with CaptureSession(self.opt, self.device) as session, session.graph() as g:
+            loss = self._body(batch, self._pos, self._y, self._f)
+        self._captured = CapturedStep(g, self._refreshed, loss=loss)
         return g
 
     def step_graph(self, positions, y, force):
@@ -141,10 +128,8 @@ class ForceTrainer:
         self._pos.copy_(positions, non_blocking=True)
         self._y.copy_(y.view(-1), non_blocking=True)
         self._f.copy_(force, non_blocking=True)
-        wcache.sync_weight_copies()           # parameters edited from outside since the last step (load_state_dict, ...)
-        self._graph.replay()
-        wcache.weight_copies_after_replay(self._graph_wt_keys)
-        return self._loss
+        self._captured.replay()
+        return self._captured.loss
 
 
 # ---- split and statistics ------------------------------------------------------------------------------------------
@@ -209,31 +194,10 @@ class ResidentSplit:
 def load_state(model, graph_pred_linear, path, load_latest=False):
     """load_model of the script: load_latest takes `model`; otherwise `model_3D` (a pretraining checkpoint) when present,
     else `model`; `graph_pred_linear` whenever the file has it."""
-    w = torch.load(path, map_location="cpu")
-    if load_latest:
-        model.load_state_dict(w["model"])
-    elif "model_3D" in w:
-        model.load_state_dict(w["model_3D"])
-    else:
-        model.load_state_dict(w["model"])
-    if graph_pred_linear is not None and "graph_pred_linear" in w:
-        graph_pred_linear.load_state_dict(w["graph_pred_linear"])
-    return w
+    return _load_state(model, graph_pred_linear, path, MD17Trainer.LOAD_KEYS, load_latest=load_latest)
 
 
-def make_scheduler(lr_scheduler, base_lrs, epochs, lr_decay_step_size, lr_decay_factor):
-    """The per-epoch schedulers of the script (:297-321): CosineAnnealingLR(epochs) or StepLR; None for anything else
-    that is not one of the two per-iteration / metric schedulers, which are refused."""
-    if lr_scheduler in ("CosineAnnealingWarmRestarts", "ReduceLROnPlateau"):
-        raise NotImplementedError(f"lr_scheduler={lr_scheduler!r} is not supported: CosineAnnealingLR, StepLR or None")
-    if lr_scheduler == "CosineAnnealingLR":
-        return CosineAnnealing(base_lrs, epochs)
-    if lr_scheduler == "StepLR":
-        return StepDecay(base_lrs, lr_decay_step_size, lr_decay_factor)
-    return None
-
-
-class MD17Trainer:
+class MD17Trainer(FineTuner):
     """examples/finetune_MD17.py's training loop, evaluation and checkpoints on the device.  model: geom3d.SchNet (with
     graph_pred_linear = nn.Linear(emb_dim, 1)) or geom3d.PaiNN (with model.create_output_layers()).  normalization: None or
     (ENERGY_MEAN_TOTAL, FORCE_MEAN_TOTAL, NUM_ATOM) of energy_force_normalization.  SchNet runs its full batches as
@@ -255,9 +219,7 @@ class MD17Trainer:
                  lr_decay_step_size=100, lr_decay_factor=0.5, energy_coeff=0.05, force_coeff=0.95, normalization=None,
                  train_batch_size=1):
         self.model, self.head = model, graph_pred_linear
-        self.device = next(model.parameters()).device
-        if self.device.type != "cuda":
-            raise RuntimeError("moleculesde_amd.finetune_md17 runs on the HIP device only (no CPU fallback)")
+        self.device = hip_device(next(model.parameters()), "finetune_md17")
         self.is_painn = type(model).__name__ == "PaiNN"
         self.energy_coeff, self.force_coeff = float(energy_coeff), float(force_coeff)
         self.epochs, self.train_batch_size = int(epochs), int(train_batch_size)
@@ -297,14 +259,7 @@ class MD17Trainer:
         return b
 
     def _painn_edges(self, batch, positions):
-        """PaiNN's radius_edge_index of these positions (MoleculeDataset3DRadius builds it per conformation).  The old index
-        stays alive while the new one is made, so the model's edge-plan cache (keyed by address) cannot see a reused one."""
-        from . import plan as _pl
-        pl = _pl.get_plan(batch)
-        rp, _ = hip.radius_plan(positions.detach(), pl.batch_i32, pl.mol_ptr, self.model.cutoff, pl.E_r_cap, 32,
-                                n_max=getattr(pl, "N_max", None))
-        keep = rp.src >= 0
-        batch.radius_edge_index = torch.stack([rp.src[keep], rp.dst[keep]]).long()
+        painn_radius_edges(self.model, batch, positions.detach())
 
     # ---- the step (train(), :34-88) and the evaluated batch (eval(), :93-142) ------------------------------------
     def _train_body(self, batch, positions, y, force):
@@ -320,11 +275,8 @@ class MD17Trainer:
             # PaiNN's embedding masks its padding row with a gradient hook that needs the gradient at once (finetune_qm9)
             torch.autograd.backward([energy, dE], [g_e, g_d])
         else:
-            slabs.begin_param_grad_batch(self.opt.params)
-            try:
+            with slabs.param_grad_batch(self.opt.params):
                 torch.autograd.backward([energy, dE], [g_e, g_d])
-            finally:
-                slabs.finish_param_grad_batch()
         self.opt.step_from_grads()
         self._refreshed = wcache.refresh_weight_t()
         return loss
@@ -347,16 +299,6 @@ class MD17Trainer:
         return loss
 
     # ---- captured graphs ---------------------------------------------------------------------------------------------
-    def _snapshot(self):
-        o = self.opt
-        return [t.clone() for t in (o.flat_p, o.m, o.v, o.step_dev, self.loss_acc)]
-
-    def _restore(self, snap):
-        o = self.opt
-        for t, s in zip((o.flat_p, o.m, o.v, o.step_dev, self.loss_acc), snap):
-            t.copy_(s)
-        wcache.invalidate_weight_copies()
-
     def _capture(self, split, kind, B, stride):
         """{gather the next batch, train step or evaluated batch} as one hipGraph on static buffers.  Warm-up runs first
         (sizes workspaces); the train warm-up's update is undone, so capturing trains nothing."""
@@ -364,51 +306,37 @@ class MD17Trainer:
             raise NotImplementedError("PaiNN runs the eager step and evaluation only (its radius graph is built per batch)")
         NA = split.num_atoms
         dev = self.device
-        st = {"pos": torch.zeros(B * NA, 3, device=dev), "y": torch.zeros(B, device=dev),
-              "f": torch.zeros(B * NA, 3, device=dev), "split": split, "B": B}
+        pos, y, f = torch.zeros(B * NA, 3, device=dev), torch.zeros(B, device=dev), torch.zeros(B * NA, 3, device=dev)
         b = self._template(split, B)
         train = kind == "train"
-        if train:
-            st["perm"] = torch.arange(len(split), dtype=torch.int32, device=dev)
-            ctr = self._train_ctr
-        else:
-            st["perm"] = None
-            ctr = self._eval_ctr
+        perm = torch.arange(len(split), dtype=torch.int32, device=dev) if train else None
+        ctr = self._train_ctr if train else self._eval_ctr
 
         def body():
-            hip.md17_gather_batch(split.pos, split.y, split.force, st["perm"], ctr, stride, st["pos"], st["y"], st["f"])
+            hip.md17_gather_batch(split.pos, split.y, split.force, perm, ctr, stride, pos, y, f)
             if train:
-                return self._train_body(b, st["pos"], st["y"], st["f"])
-            self._eval_body(b, st["pos"], st["y"], st["f"], self.eval_acc)
+                return self._train_body(b, pos, y, f)
+            self._eval_body(b, pos, y, f, self.eval_acc)
             return None
 
-        snap = self._snapshot() if train else None
+        snap = optimizer_snapshot(self.opt, self.loss_acc) if train else None
         ctr.zero_()
         for _ in range(2 if train else 1):
             body()
+        with CaptureSession(self.opt if train else None, dev) as session, session.graph() as g:
+            loss = body()
         if train:
-            self.opt.new_table_slot()
-            slabs.new_param_grad_slot(dev)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with slabs.no_gc(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-            st["loss"] = body()
-        slabs.flush_table_uploads()
-        if train:
-            self.opt.use_eager_slot()
-            slabs.use_eager_param_grad_slot()
-            st["keys"] = self._refreshed
             torch.cuda.synchronize()
-            self._restore(snap)
-        st["graph"] = g
+            optimizer_restore(self.opt, snap, self.loss_acc)
         ctr.zero_()
         self.eval_acc.zero_()
-        return st
+        # (the static buffers the graph reads and writes live as long as its record)
+        return CapturedStep(g, self._refreshed if train else None, split=split, perm=perm, loss=loss, buffers=(pos, y, f))
 
     def _graph(self, split, kind, B, stride):
         key = (kind, id(split), B, stride)
         st = self._graphs.get(key)
-        if st is None or st["split"] is not split:
+        if st is None or st.split is not split:
             st = self._graphs[key] = self._capture(split, kind, B, stride)
         return st
 
@@ -427,14 +355,11 @@ class MD17Trainer:
             st = self._graph(split, "train", bs, bs)
         self.loss_acc.zero_()
         if use_graph:
-            st["perm"].copy_(perm.to(torch.int32))
+            st.perm.copy_(perm.to(torch.int32))
             self._train_ctr.zero_()
-            g, keys = st["graph"], st["keys"]
             for _ in range(n_full):
-                wcache.sync_weight_copies()
-                g.replay()
-                wcache.weight_copies_after_replay(keys)
-            self.last_loss = st["loss"]
+                st.replay()
+            self.last_loss = st.loss
         else:
             perm_d = perm.to(self.device)
             for k in range(n_full):
@@ -444,11 +369,6 @@ class MD17Trainer:
         acc = float(self.loss_acc.item())
         self.scheduler_step()
         return acc / (n_full + (1 if rem else 0))
-
-    def scheduler_step(self):
-        """lr_scheduler.step() once per epoch (StepLR, CosineAnnealingLR): the new rates into FlatAdam's device table."""
-        if self.scheduler is not None:
-            self.opt.set_lr(self.scheduler.step())
 
     def evaluate(self, split, batch_size=128, captured=None):
         """eval() (:93-142): (energy MAE, force MAE) over the split in loader order.  SchNet: one captured graph per batch
@@ -469,7 +389,7 @@ class MD17Trainer:
             for item in sts:
                 if item is not None:
                     for _ in range(item[1]):
-                        item[0]["graph"].replay()
+                        item[0].graph.replay()
         else:
             acc.zero_()
             ar = torch.arange(M, device=self.device)
@@ -522,12 +442,7 @@ class MD17Trainer:
         h.update(best_val_idx=best_val_idx, best_test_energy=best_test[0], best_test_force=best_test[1])
         return h
 
-    # ---- checkpoints -------------------------------------------------------------------------------------------------
+    # ---- checkpoints: scheduler_step and save_model (:163-186) are finetune_common.FineTuner's --------------------------
     def load_model(self, path, load_latest=False):
-        with torch.no_grad():
-            load_state(self.model, self.head, path, load_latest)
-        wcache.bump_weight_epoch()
-
-    def save_model(self, path):
-        """{"model", "graph_pred_linear"} (save_model, :163-186)."""
-        torch.save(checkpoint_dict(self.model, self.head), path)
+        """load_model (:145-160): see load_state."""
+        self._load_model(path, load_latest)

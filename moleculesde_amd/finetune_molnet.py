@@ -15,13 +15,12 @@ the loss is hip.molnet_bce (fp64, one launch).  The step reads 3 numbers back to
 as the reference's loss.item() does.  Batches have exact sizes (host-built plans, geom3d.prepare_batch): MoleculeNet
 molecules exceed the 32-atom bound of the device plan builder, so the step is launched eagerly, one batch at a time.
 """
-import math
-
 import numpy as np
 import torch
 
 from . import _lib, hip, plan as _plan, slabs, wcache
 from ._torchabi import _p, _stream
+from .finetune_common import CosineAnnealing, FineTuner, checkpoint_dict, hip_device, load_state as _load_state  # noqa: F401
 from .optim import FlatAdam
 
 # examples/util.py:183-199
@@ -110,57 +109,23 @@ def roc_auc_tasks(y_true, y_scores, y_valid):
     return (sum(kept) / len(kept) if kept else float("nan")), per
 
 
-# ---- CosineAnnealingLR(optimizer, T_max), eta_min = 0, stepped once per epoch ----------------------------------------------
-class CosineAnnealing:
-    """The learning rates torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max) gives after each step(): the same recursive
-    update as torch's get_lr, so the values agree to the last bit, not only to the closed form."""
-
-    def __init__(self, base_lrs, T_max, eta_min=0.0):
-        self.base_lrs = [float(v) for v in base_lrs]
-        self.lrs = list(self.base_lrs)
-        self.T_max, self.eta_min, self.last_epoch = int(T_max), float(eta_min), 0
-
-    def step(self):
-        self.last_epoch += 1
-        e, T, lo = self.last_epoch, self.T_max, self.eta_min
-        if (e - 1 - T) % (2 * T) == 0:
-            self.lrs = [lr + (b - lo) * (1 - math.cos(math.pi / T)) / 2 for lr, b in zip(self.lrs, self.base_lrs)]
-        else:
-            self.lrs = [(1 + math.cos(math.pi * e / T)) / (1 + math.cos(math.pi * (e - 1) / T)) * (lr - lo) + lo
-                        for lr in self.lrs]
-        return list(self.lrs)
-
-
 # ---- checkpoints (finetune_MoleculeNet.py:71-102) -------------------------------------------------------------------------
 def load_state(model, path):
     """load_model of the script: a checkpoint with `model_2D` (pretrain.Trainer.save), `model`, or a raw state dict."""
-    w = torch.load(path, map_location="cpu")
-    if "model_2D" in w:
-        model.load_state_dict(w["model_2D"])
-    elif "model" in w:
-        model.load_state_dict(w["model"])
-    else:
-        model.load_state_dict(w)
-    return w
+    return _load_state(model, None, path, MoleculeNetTrainer.LOAD_KEYS, raw_ok=True)
 
 
-def checkpoint_dict(model, graph_pred_linear):
-    """save_model of the script: {"model": ..., "graph_pred_linear": ...}."""
-    d = {"model": model.state_dict()}
-    if graph_pred_linear is not None:
-        d["graph_pred_linear"] = graph_pred_linear.state_dict()
-    return d
+class MoleculeNetTrainer(FineTuner):
+    # of finetune_common.FineTuner: scheduler_step (:152-153), save_model (:83-102: model.pth for the best epoch,
+    # model_final.pth for the last) and load_model (:71-80: model_2D, model or a raw state dict, into the GIN only)
+    LOAD_KEYS, RAW_OK, LOADS_HEAD = ("model_2D", "model"), True, False
 
-
-class MoleculeNetTrainer:
     def __init__(self, model, graph_pred_linear, lr=1e-4, weight_decay=0.0, epochs=100, lr_scheduler="CosineAnnealingLR",
                  seed=42):
         """model: geom3d.GNN on the HIP device; graph_pred_linear: torch.nn.Linear(intermediate_dim, num_tasks).  Adam over the
         script's two param groups (:273-278), CosineAnnealingLR(epochs) per epoch when lr_scheduler says so (config.py:52)."""
         self.model, self.head = model, graph_pred_linear
-        self.device = next(model.parameters()).device
-        if self.device.type != "cuda":
-            raise RuntimeError("moleculesde_amd.finetune_molnet runs on the HIP device only (no CPU fallback)")
+        self.device = hip_device(next(model.parameters()), "finetune_molnet")
         if lr_scheduler not in ("CosineAnnealingLR", None, "None"):
             raise NotImplementedError(f"lr_scheduler={lr_scheduler!r}: CosineAnnealingLR (the default) or None")
         self.opt = FlatAdam([{"params": model.parameters(), "lr": lr}, {"params": graph_pred_linear.parameters(), "lr": lr}],
@@ -196,11 +161,8 @@ class MoleculeNetTrainer:
         if self.last_skipped:
             return loss
         self.opt.zero_grad()
-        slabs.begin_param_grad_batch(self.opt.params)
-        try:
+        with slabs.param_grad_batch(self.opt.params):
             torch.autograd.backward(logits, dlogits)
-        finally:
-            slabs.finish_param_grad_batch()
         self.opt.step_from_grads()
         wcache.refresh_weight_t()
         return loss
@@ -216,11 +178,6 @@ class MoleculeNetTrainer:
             n += 1
         self.scheduler_step()
         return acc / max(n, 1)
-
-    def scheduler_step(self):
-        """lr_scheduler.step() once per epoch (:152-153): the new rates go into FlatAdam's per-group table on the device."""
-        if self.scheduler is not None:
-            self.opt.set_lr(self.scheduler.step())
 
     # ---- evaluation ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -246,15 +203,3 @@ class MoleculeNetTrainer:
         y_true, y_scores, y_valid = self.predict(batches)
         mean, _ = roc_auc_tasks(y_true, y_scores, y_valid)
         return mean, y_true, y_scores
-
-    # ---- checkpoints ---------------------------------------------------------------------------------------------------
-    def load_model(self, path):
-        """load_model (:71-80): `model_2D` (a pretraining checkpoint), `model`, or a raw state dict, into the GIN."""
-        with torch.no_grad():
-            load_state(self.model, path)
-        wcache.bump_weight_epoch()
-
-    def save_model(self, path):
-        """save_model (:83-102): {"model": GIN state dict, "graph_pred_linear": head state dict} at `path` (the script names
-        it model.pth for the best epoch, model_final.pth for the last)."""
-        torch.save(checkpoint_dict(self.model, self.head), path)

@@ -20,7 +20,9 @@ import numpy as np
 import torch
 
 from . import bucket as BK, hip, slabs, wcache
-from .finetune_molnet import CosineAnnealing
+from .capture import CaptureSession, CapturedStep, optimizer_restore, optimizer_snapshot
+from .finetune_common import (CosineAnnealing, FineTuner, StepDecay, checkpoint_dict, hip_device,  # noqa: F401
+                              load_state as _load_state, make_scheduler, painn_radius_edges)
 from .optim import FlatAdam
 
 # Geom3D/datasets/dataset_QM9.py:43-57
@@ -77,39 +79,11 @@ def mean_absolute_error(pred, target):
     return np.mean(np.abs(pred - target))
 
 
-# ---- StepLR(optimizer, step_size, gamma), stepped once per epoch ------------------------------------------------------------
-class StepDecay:
-    """The learning rates torch.optim.lr_scheduler.StepLR(opt, step_size, gamma) gives after each step(): torch's recursive
-    form (lr * gamma at every multiple of step_size), bit for bit."""
-
-    def __init__(self, base_lrs, step_size, gamma=0.1):
-        self.lrs = [float(v) for v in base_lrs]
-        self.step_size, self.gamma, self.last_epoch = int(step_size), float(gamma), 0
-
-    def step(self):
-        self.last_epoch += 1
-        if self.last_epoch % self.step_size == 0:
-            self.lrs = [lr * self.gamma for lr in self.lrs]
-        return list(self.lrs)
-
-
 # ---- checkpoints (finetune_QM9.py:95-130) -------------------------------------------------------------------------------
-def checkpoint_dict(model, graph_pred_linear):
-    """save_model of the script: {"model": ..., "graph_pred_linear": ...}."""
-    d = {"model": model.state_dict()}
-    if graph_pred_linear is not None:
-        d["graph_pred_linear"] = graph_pred_linear.state_dict()
-    return d
-
-
 def load_state(model, graph_pred_linear, path):
     """load_model of the script: `model_3D` (a pretraining checkpoint, pretrain.Trainer.save) or `model`, plus
     `graph_pred_linear` when the file has it."""
-    w = torch.load(path, map_location="cpu")
-    model.load_state_dict(w["model_3D"] if "model_3D" in w else w["model"])
-    if graph_pred_linear is not None and "graph_pred_linear" in w:
-        graph_pred_linear.load_state_dict(w["graph_pred_linear"])
-    return w
+    return _load_state(model, graph_pred_linear, path, QM9Trainer.LOAD_KEYS)
 
 
 def save_evaluation_best(output_model_dir, val_target, val_pred, test_target, test_pred):
@@ -128,7 +102,9 @@ def check_rotation_transform(use_rotation_transform):
                                   "distances only, the transform changes nothing but rounding")
 
 
-class QM9Trainer:
+class QM9Trainer(FineTuner):
+    # of finetune_common.FineTuner: scheduler_step, load_model (:95-108: model_3D or model, plus graph_pred_linear if present)
+    # and save_model (:111-130: model.pth for the best validation MAE, model_final.pth for the last epoch)
     def __init__(self, model, graph_pred_linear, lr=1e-4, weight_decay=0.0, epochs=100, loss="mae",
                  lr_scheduler="CosineAnnealingLR", train_mean=0.0, train_std=1.0, task_id=None, lr_decay_step_size=100,
                  lr_decay_factor=0.5, use_rotation_transform=False):
@@ -139,25 +115,14 @@ class QM9Trainer:
         if loss not in hip.QM9_LOSS_MODES:
             raise ValueError("Loss {} not included.".format(loss))
         self.model, self.head = model, graph_pred_linear
-        self.device = next(model.parameters()).device
-        if self.device.type != "cuda":
-            raise RuntimeError("moleculesde_amd.finetune_qm9 runs on the HIP device only (no CPU fallback)")
+        self.device = hip_device(next(model.parameters()), "finetune_qm9")
         self.is_painn = type(model).__name__ == "PaiNN"
         if not self.is_painn and not (isinstance(graph_pred_linear, torch.nn.Linear) and graph_pred_linear.out_features == 1):
             raise ValueError("SchNet fine-tuning takes graph_pred_linear = torch.nn.Linear(emb_dim, 1)")
-        if lr_scheduler in ("ReduceLROnPlateau", "CosineAnnealingWarmRestarts"):
-            raise NotImplementedError(f"lr_scheduler={lr_scheduler!r} is not supported: CosineAnnealingLR, StepLR or None")
-        if lr_scheduler not in ("CosineAnnealingLR", "StepLR", None, "None"):
-            raise ValueError(f"lr scheduler {lr_scheduler!r} is not included")
+        self.scheduler = make_scheduler(lr_scheduler, [lr, lr], epochs, lr_decay_step_size, lr_decay_factor, strict=True)
         self.loss, self.mean, self.std, self.task_id = loss, float(train_mean), float(train_std), task_id
         self.opt = FlatAdam([{"params": model.parameters(), "lr": lr}, {"params": graph_pred_linear.parameters(), "lr": lr}],
                             weight_decay=weight_decay)
-        if lr_scheduler == "CosineAnnealingLR":
-            self.scheduler = CosineAnnealing([lr, lr], epochs)
-        elif lr_scheduler == "StepLR":
-            self.scheduler = StepDecay([lr, lr], lr_decay_step_size, lr_decay_factor)
-        else:
-            self.scheduler = None
         dev = self.device
         self.loss_acc = torch.zeros(1, dtype=torch.float64, device=dev)     # device-side sum of the epoch's step losses
         if not self.is_painn:
@@ -183,13 +148,7 @@ class QM9Trainer:
             return self.model(batch.x, batch.positions, batch.batch)
         ei = getattr(batch, "radius_edge_index", None)
         if ei is None:
-            from . import plan as _pl
-            pl = _pl.get_plan(batch)
-            rp, _ = hip.radius_plan(batch.positions, pl.batch_i32, pl.mol_ptr, self.model.cutoff, pl.E_r_cap, 32,
-                                    n_max=getattr(pl, "N_max", None))
-            keep = rp.src >= 0
-            ei = torch.stack([rp.src[keep], rp.dst[keep]]).long()
-            batch.radius_edge_index = ei
+            ei = painn_radius_edges(self.model, batch, batch.positions)
         return self.model(batch.x, batch.positions, ei, batch.batch)
 
     # ---- one training step ---------------------------------------------------------------------------------------------
@@ -214,11 +173,8 @@ class QM9Trainer:
             # over, not after a deferred slab reduction: plain backward, weight gradients launched one by one
             torch.autograd.backward(roots, grads)
         else:
-            slabs.begin_param_grad_batch(self.opt.params)
-            try:
+            with slabs.param_grad_batch(self.opt.params):
                 torch.autograd.backward(roots, grads)
-            finally:
-                slabs.finish_param_grad_batch()
         if not self.is_painn:
             self.head.weight.grad, self.head.bias.grad = self._gW, self._gb
         self.opt.step_from_grads()
@@ -237,16 +193,6 @@ class QM9Trainer:
     def make_bucket(self, caps):
         return BK.Bucket(caps, self.device, node_class=self.model.node_class, z_only=True)
 
-    def _snapshot(self):
-        o = self.opt
-        return [t.clone() for t in (o.flat_p, o.m, o.v, o.step_dev, self.loss_acc)]
-
-    def _restore(self, snap):
-        o = self.opt
-        for t, s in zip((o.flat_p, o.m, o.v, o.step_dev, self.loss_acc), snap):
-            t.copy_(s)
-        wcache.invalidate_weight_copies()
-
     def capture_bucket(self, bk, warm_blob, eager_steps=1):
         """Warm up on one raw batch (sizes the workspaces), then capture {device-side plan construction + step} for the
         bucket's capacities.  The warm-up steps are undone (parameters, Adam moments, step count and the epoch's loss sum
@@ -258,25 +204,18 @@ class QM9Trainer:
         ok, sizes = bk.check()
         if not ok:
             raise BK.BucketOverflow(f"batch does not fit the bucket: {sizes} vs {bk.caps.as_dict()}")
-        snap = self._snapshot()
+        snap = optimizer_snapshot(self.opt, self.loss_acc)
         with bk.bounds():
             for _ in range(eager_steps):
                 self._step_body(bk.batch, bk.y)
-        self.opt.new_table_slot()
-        slabs.new_param_grad_slot(self.device)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
-        with slabs.no_gc(), bk.bounds(), torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode="thread_local"):
+        with CaptureSession(self.opt, self.device, self._graph_pool) as session, session.graph(bk.bounds()) as g:
             bk.build_plan_on_device()
             pred, loss = self._step_body(bk.batch, bk.y)
-        slabs.flush_table_uploads()
-        self.opt.use_eager_slot()
-        slabs.use_eager_param_grad_slot()
-        self._graphs[id(bk)] = (g, bk, pred, loss, self._last_refreshed)
+        self._graphs[id(bk)] = CapturedStep(g, self._last_refreshed, bucket=bk, pred=pred, loss=loss)
         torch.cuda.synchronize()
-        self._restore(snap)
+        optimizer_restore(self.opt, snap, self.loss_acc)
         return g
 
     def step_bucket(self, bk, blob):
@@ -291,13 +230,11 @@ class QM9Trainer:
 
     def replay(self, bk):
         """The captured step on whatever the bucket's raw buffer holds (a blob loaded by bk.load or a BlobFeeder)."""
-        g, held, pred, loss, keys = self._graphs[id(bk)]
-        assert held is bk
-        wcache.sync_weight_copies()
-        g.replay()
-        wcache.weight_copies_after_replay(keys)
-        self.last_pred, self.last_loss = pred, loss
-        return loss
+        rec = self._graphs[id(bk)]
+        assert rec.bucket is bk
+        rec.replay()
+        self.last_pred, self.last_loss = rec.pred, rec.loss
+        return rec.loss
 
     def fits(self, bk, batch):
         need = BK.raw_sizes_z(batch)
@@ -333,11 +270,6 @@ class QM9Trainer:
         acc = float(self.loss_acc.item())
         self.scheduler_step()
         return acc / max(n, 1)
-
-    def scheduler_step(self):
-        """lr_scheduler.step() once per epoch: the new rates go into FlatAdam's per-group table on the device."""
-        if self.scheduler is not None:
-            self.opt.set_lr(self.scheduler.step())
 
     # ---- evaluation ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -381,15 +313,3 @@ class QM9Trainer:
         y_scores = torch.cat(preds).cpu().numpy()
         a = acc.cpu().tolist()
         return a[0] / max(a[1], 1.0), y_true, y_scores
-
-    # ---- checkpoints ---------------------------------------------------------------------------------------------------
-    def load_model(self, path):
-        """load_model (:95-108): `model_3D` (a pretraining checkpoint) or `model`, plus `graph_pred_linear` if present."""
-        with torch.no_grad():
-            load_state(self.model, self.head, path)
-        wcache.bump_weight_epoch()
-
-    def save_model(self, path):
-        """save_model (:111-130): {"model", "graph_pred_linear"} at `path` (model.pth for the best validation MAE,
-        model_final.pth for the last epoch)."""
-        torch.save(checkpoint_dict(self.model, self.head), path)

@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from . import dp, slabs, wcache
+from .capture import CaptureSession, CapturedStep
 from .geom3d import GNN, SchNet, SDEModel2Dto3D_01, SDEModel2Dto3D_02, prepare_batch
 from .geom3d import nn as _nn
 from .optim import FlatAdam
@@ -331,12 +332,9 @@ class Trainer:
         # 2D branch 4.55 ms, a third stream for the 2D->3D coordinate branch 4.73 ms, weight gradients on a fourth
         # 5.4 ms -- the step is a chain of small kernels and every extra queue / cross-stream event costs more
         # dispatch latency than it hides.  Two streams it is.
-        self._graphs = {}
+        self._graphs = {}                 # id(batch) -> capture.CapturedStep (batch, with_adam, tails, keys, loss)
         self.adam_outside_graph = False   # True reproduces the multi-GPU structure (graph; all-reduce; Adam) on 1 GPU
         self._graph_pool = None
-        self._graph_loss = {}
-        self._graph_wt_keys = {}
-        self._graph_tails = {}            # data-parallel overlap: the per-bucket tail graphs of a captured step
         self.step_counter = torch.zeros(1, dtype=torch.int64, device=device)
 
     def _side_geometry(self, on):
@@ -358,14 +356,8 @@ class Trainer:
             return m3(batch.x[:, 0], batch.positions, batch.batch, return_latent=True)
         ei = getattr(batch, "radius_edge_index", None)
         if ei is None:
-            from . import hip, plan as _pl
-            pl = _pl.get_plan(batch)
-            rp, _ = hip.radius_plan(batch.positions, pl.batch_i32, pl.mol_ptr, m3.cutoff, pl.E_r_cap, 32, n_max=getattr(pl, "N_max", None))
-            keep = rp.src >= 0                                    # host sync: PaiNN batches are not graph-captured
-            # PyG radius_graph orientation: row 0 = source, row 1 = target (the 32-neighbour cap applies per TARGET);
-            # PaiNN aggregates at row 0 (painn.py:235), i.e. at the source, exactly as the reference does
-            ei = torch.stack([rp.src[keep], rp.dst[keep]]).long()
-            batch.radius_edge_index = ei
+            from .finetune_common import painn_radius_edges      # (shared with the fine-tuning loops, which build it too)
+            ei = painn_radius_edges(m3, batch, batch.positions)
         return m3(batch.x[:, 0], batch.positions, ei, batch.batch, return_latent=True)
 
     def losses(self, batch, log=False, split_roots=False):
@@ -735,72 +727,60 @@ class Trainer:
         captured in front of the step (a bucket's device-side plan construction)."""
         key = id(batch)
         if key in self._graphs:
-            return self._graphs[key][0]
+            return self._graphs[key].graph
         with_adam = not self._use_dp() and not self.adam_outside_graph
         sd = self.step_counter.view(torch.int64)
         self.models["SDE_2Dto3D_model"].score_network.seed_dev = sd
         if hasattr(self.noise, "seed_dev"):
             self.noise.seed_dev = sd        # fresh contrastive negatives on every replay
-        self.opt.new_table_slot()       # this graph's own (pinned) gradient chunk table
         from . import hip as _hip
-        slabs.new_param_grad_slot(batch.x.device)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
-        # thread_local: other threads of the process (the RCCL watchdog under DP) may issue HIP calls
-        # while this thread captures; they must not invalidate the capture
         # (round 4: capturing on a high-priority stream -- main chain over the second stream -- changes nothing: 2.575 vs 2.582 ms)
         overlap = (not with_adam) and self._use_dp() and DP_OVERLAP and self.dp_buckets
         tail_graphs = None
-        with slabs.no_gc(), self._bounds(batch), torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode="thread_local"):
-            if pre is not None:
-                pre()
-            loss = self._graph_body(batch, with_adam, finish=not overlap)
-        if overlap:
-            # the data-parallel tail as one more captured piece per bucket (weight gradients of the bucket, their slab
-            # reduction, its rows of the flat gradient buffer): step_graph() issues the bucket's all-reduce behind each piece
-            # (_dp_tail).  Same memory pool, replayed in capture order.
-            order = self._dp_order()
-            slabs.partition_param_grad_batch(self.opt.grad_bucket_lookup(), len(self.opt.bucket_ranges))
-            table = self.opt.grad_table()
-            tail_graphs = []
-            for k, i in enumerate(order):
-                gk = torch.cuda.CUDAGraph()
-                with slabs.no_gc(), self._bounds(batch), torch.cuda.graph(gk, pool=self._graph_pool, capture_error_mode="thread_local"):
-                    self._dp_finish_bucket(i, table)
-                    if k == len(order) - 1:
-                        slabs.finish_param_grad_batch()
-                        _hip.stamp("wgrad_end")
-                tail_graphs.append(gk)
-        slabs.flush_table_uploads()      # the graph's pointer tables: uploaded once, not at every replay
-        self.opt.use_eager_slot()
-        slabs.use_eager_param_grad_slot()
+        with CaptureSession(self.opt, batch.x.device, self._graph_pool) as session:
+            with session.graph(self._bounds(batch)) as g:
+                if pre is not None:
+                    pre()
+                loss = self._graph_body(batch, with_adam, finish=not overlap)
+            if overlap:
+                # the data-parallel tail as one more captured piece per bucket (weight gradients of the bucket, their slab
+                # reduction, its rows of the flat gradient buffer): step_graph() issues the bucket's all-reduce behind each
+                # piece (_dp_tail).  Same memory pool, replayed in capture order.
+                order = self._dp_order()
+                slabs.partition_param_grad_batch(self.opt.grad_bucket_lookup(), len(self.opt.bucket_ranges))
+                table = self.opt.grad_table()
+                tail_graphs = []
+                for k, i in enumerate(order):
+                    with session.graph(self._bounds(batch)) as gk:
+                        self._dp_finish_bucket(i, table)
+                        if k == len(order) - 1:
+                            slabs.finish_param_grad_batch()
+                            _hip.stamp("wgrad_end")
+                    tail_graphs.append(gk)
         # the captured batch is held strongly: its tensors' addresses are baked into the graph, and a live reference
-        # keeps id(batch) from being recycled for a different batch
-        self._graphs[key] = (g, batch, with_adam)
-        self._graph_tails[key] = tail_graphs
-        # the weight copies the captured refresh launch re-lays-out at every replay (wcache.weight_copies_after_replay)
-        self._graph_wt_keys[key] = getattr(self, "_last_refreshed", ()) if with_adam else None
-        self._graph_loss[key] = loss
+        # keeps id(batch) from being recycled for a different batch.  keys: the weight copies the captured refresh launch
+        # re-lays-out at every replay (wcache.weight_copies_after_replay)
+        self._graphs[key] = CapturedStep(g, getattr(self, "_last_refreshed", ()) if with_adam else None, batch=batch,
+                                         with_adam=with_adam, tails=tail_graphs, loss=loss)
         return g
 
     def step_graph(self, batch):
         """Replay the captured step; under DP the all-reduce and Adam run after the replay."""
-        g, held, with_adam = self._graphs[id(batch)]
-        assert held is batch
-        from . import hip as _hip
+        rec = self._graphs[id(batch)]
+        assert rec.batch is batch
+        with_adam, tails = rec.with_adam, rec.tails
         wcache.sync_weight_copies()          # parameters edited from outside since the last step (load_state_dict, ...)
         timing = self.dp_timing is not None and not with_adam and self._use_dp() and self.dp_buckets
         if timing:                         # [replay start, replay end, (bucket reduced, bucket's Adam done) x buckets]
             self._tm_cur = [self._timing_event()]
             self.dp_timing.append(self._tm_cur)
-        g.replay()
-        tails = self._graph_tails.get(id(batch))
+        rec.graph.replay()
         if timing and tails is None:
             self._tm_cur.append(self._timing_event())
-        if self._graph_wt_keys.get(id(batch)) is not None:
-            wcache.weight_copies_after_replay(self._graph_wt_keys[id(batch)])
+        if rec.keys is not None:
+            wcache.weight_copies_after_replay(rec.keys)
         for bn in self._bn_modules:
             bn.pending_batches += 1        # the captured forward does not run Python: count its BatchNorm calls here
         if not with_adam:
@@ -818,7 +798,7 @@ class Trainer:
                 self.opt.step()
                 self._refresh_weights()
         self.steps += 1
-        return self._graph_loss[id(batch)]
+        return rec.loss
 
     # ---- capacity buckets: ONE captured graph for every batch (moleculesde_amd/bucket.py) ------------------------
     def make_bucket(self, caps):
@@ -849,10 +829,7 @@ class Trainer:
             self.step(bk.batch)
         if split_plan:
             # the plan construction as a graph of its own (BucketPipeline runs it for batch t+1 beside the step of batch t)
-            torch.cuda.synchronize()
-            bk.plan_graph = torch.cuda.CUDAGraph()
-            from . import hip as _hipg
-            with slabs.no_gc(), torch.cuda.graph(bk.plan_graph, capture_error_mode="thread_local"):
+            with CaptureSession(None, self.device) as session, session.graph() as bk.plan_graph:
                 bk.build_plan_on_device(None)
             return self.capture(bk.batch)
         side = self._side_stream if (self.overlap_streams and PLAN_LISTS_ON_SIDE) else None
@@ -976,9 +953,6 @@ class StreamRunner:
             # (the superseded graph is parked, not destroyed: freeing a graph of the shared memory pool while another capture
             # into that pool follows trips an allocator assertion in this torch build; it is a few hundred nodes)
             self._parked = getattr(self, "_parked", []) + [self.tr._graphs.pop(id(self.bk.batch), None)]
-            self._parked.append(self.tr._graph_tails.pop(id(self.bk.batch), None))
-            self.tr._graph_loss.pop(id(self.bk.batch), None)
-            self.tr._graph_wt_keys.pop(id(self.bk.batch), None)
             self.tr.capture(self.bk.batch, pre=lambda: self.bk.build_plan_on_device(
                 self.tr._side_stream if (self.tr.overlap_streams and PLAN_LISTS_ON_SIDE) else None))
             self._captured_coeffs = self._coeffs()

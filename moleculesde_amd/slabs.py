@@ -9,6 +9,7 @@ longer re-exports it).
     (include/msde_hip.h: msde_linear_bwd_w_grouped_ex, msde_reduce_slabs_multi), deferred leaf kernels, table slots;
   * weight_grad / weight_grad_leaf / weight_grad_blocks / colsum: the entry points the autograd functions call.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -500,6 +501,16 @@ def finish_param_grad_batch():
     """Sum all queued slabs (one launch on the current stream, which must already be ordered after every stream
     that ran part of the backward -- loss.backward() returns in that state)."""
     _SLABS.finish()
+
+
+@contextlib.contextmanager
+def param_grad_batch(params=None):
+    """`with param_grad_batch(params): backward` -- begin_param_grad_batch, and finish_param_grad_batch however it ends."""
+    begin_param_grad_batch(params)
+    try:
+        yield
+    finally:
+        finish_param_grad_batch()
 
 
 def new_param_grad_slot(device):

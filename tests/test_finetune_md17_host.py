@@ -105,6 +105,18 @@ def test_load_model_rules(tmp_path):
     assert _eq(mt, m3) and all(torch.equal(h_before[k], v) for k, v in ht.state_dict().items())
     # head None (a model without graph_pred_linear)
     FM.load_state(mt, None, path)
+    # the shared load_state with MD17's key order gives the same three rules
+    from moleculesde_amd import finetune_common as FC
+    assert FM.MD17Trainer.LOAD_KEYS == ("model_3D", "model") and FM.make_scheduler is FC.make_scheduler
+    torch.save({"model_3D": m1.state_dict(), "model": m2.state_dict(), "graph_pred_linear": h1.state_dict()}, path)
+    mt, ht = _nets(9)
+    FC.load_state(mt, ht, path, ("model_3D", "model"))
+    assert _eq(mt, m1) and _eq(ht, h1)
+    FC.load_state(mt, ht, path, ("model_3D", "model"), load_latest=True)
+    assert _eq(mt, m2)
+    torch.save({"model": m3.state_dict()}, path)
+    FC.load_state(mt, None, path, ("model_3D", "model"))
+    assert _eq(mt, m3) and _eq(ht, h1)
     # the saved layout
     from moleculesde_amd.finetune_qm9 import checkpoint_dict
     assert set(checkpoint_dict(m1, h1)) == {"model", "graph_pred_linear"} and set(checkpoint_dict(m1, None)) == {"model"}

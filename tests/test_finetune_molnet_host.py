@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from moleculesde_amd import finetune_common as FC
 from moleculesde_amd import finetune_molnet as FM
 from moleculesde_amd.synthetic import make_molnet_batch
 
@@ -120,10 +121,26 @@ def test_checkpoint_layouts(tmp_path):
         path = tmp_path / f"{layout}.pth"
         sd = src.state_dict()
         torch.save(sd if layout == "raw" else {layout: sd, "other": {"x": torch.zeros(1)}}, path)
-        dst = _Gnn()
-        FM.load_state(dst, path)
-        for k, v in src.state_dict().items():
-            assert torch.equal(dst.state_dict()[k], v), (layout, k)
+        # the module's load_state and the shared one with MoleculeNet's key order: never a head, a raw state dict allowed
+        h0 = torch.nn.Linear(2, 5)
+        for load in (lambda m: FM.load_state(m, path),
+                     lambda m: FC.load_state(m, None, path, ("model_2D", "model"), raw_ok=True),
+                     lambda m: FC.load_state(m, h0, path, FM.MoleculeNetTrainer.LOAD_KEYS, raw_ok=True)):
+            dst = _Gnn()
+            load(dst)
+            for k, v in src.state_dict().items():
+                assert torch.equal(dst.state_dict()[k], v), (layout, k)
+    # model_2D wins over model; without raw_ok a file with neither key is an error
+    other = _Gnn()
+    torch.save({"model": other.state_dict(), "model_2D": src.state_dict()}, tmp_path / "both.pth")
+    dst = _Gnn()
+    FM.load_state(dst, tmp_path / "both.pth")
+    assert torch.equal(dst.lin.weight, src.lin.weight)
+    with pytest.raises(KeyError):
+        FC.load_state(_Gnn(), None, tmp_path / "raw.pth", ("model_2D", "model"))
+    assert FM.MoleculeNetTrainer.LOADS_HEAD is False and FM.MoleculeNetTrainer.RAW_OK is True
+    import inspect
+    assert list(inspect.signature(FM.MoleculeNetTrainer.load_model).parameters) == ["self", "path"]      # load_latest is MD17's
 
 
 def test_num_tasks():

@@ -99,6 +99,23 @@ def test_checkpoint_layout_and_eval_file(tmp_path):
     torch.save({"model_3D": model.state_dict(), "graph_pred_linear": head.state_dict()}, str(tmp_path / "a.pth"))
     FQ.load_state(m2, h2, str(tmp_path / "a.pth"))
     assert torch.equal(m2[0].weight, model[0].weight) and torch.equal(h2.weight, head.weight)
+    # the shared load_state with QM9's key order: model_3D, then model; never a raw state dict
+    from moleculesde_amd import finetune_common as FC
+    assert FQ.QM9Trainer.LOAD_KEYS == ("model_3D", "model") and FQ.QM9Trainer.LOADS_HEAD and not FQ.QM9Trainer.RAW_OK
+    assert FQ.checkpoint_dict is FC.checkpoint_dict
+    other = torch.nn.Sequential(torch.nn.Linear(4, 3))
+    torch.save({"model_3D": model.state_dict(), "model": other.state_dict()}, str(tmp_path / "b.pth"))
+    torch.save({"model": other.state_dict()}, str(tmp_path / "c.pth"))
+    for load in (lambda m, h, p: FQ.load_state(m, h, p), lambda m, h, p: FC.load_state(m, h, p, ("model_3D", "model"))):
+        m3, h3 = torch.nn.Sequential(torch.nn.Linear(4, 3)), torch.nn.Linear(3, 1)
+        h_before = h3.weight.clone()
+        load(m3, h3, str(tmp_path / "b.pth"))
+        assert torch.equal(m3[0].weight, model[0].weight) and torch.equal(h3.weight, h_before)
+        load(m3, h3, str(tmp_path / "c.pth"))
+        assert torch.equal(m3[0].weight, other[0].weight)
+        torch.save(model.state_dict(), str(tmp_path / "raw.pth"))
+        with pytest.raises(KeyError):
+            load(m3, h3, str(tmp_path / "raw.pth"))
     path = FQ.save_evaluation_best(str(tmp_path), np.zeros(3), np.ones(3), np.zeros(2), np.ones(2))
     assert path == os.path.join(str(tmp_path), "evaluation_best.pth.npz") and os.path.exists(path)
     assert not os.path.exists(os.path.join(str(tmp_path), "evaluation_best.pth"))

@@ -236,6 +236,13 @@ def test_captured_epoch_and_evaluation_match_eager(dev, kind):
     res = {}
     for captured in (False, True):
         tr = _trainer(g, dev, kind, captured=captured)
+        if captured:                      # capturing the train graph (warm-up steps included) trains nothing
+            o, bs = tr.opt, tr.train_batch_size
+            before = [t.clone() for t in (o.flat_p, o.m, o.v, o.step_dev, tr.loss_acc)]
+            first = tr._capture(train, "train", bs, bs)
+            assert first.keys is not None
+            for t, t0 in zip((o.flat_p, o.m, o.v, o.step_dev, tr.loss_acc), before):
+                assert torch.equal(t, t0)
         out = []
         gen = torch.Generator().manual_seed(5)
         for _ in range(2):

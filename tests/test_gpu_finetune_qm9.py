@@ -231,7 +231,11 @@ def test_captured_stream_matches_eager(dev):
         tr = _small_trainer(dev)
         bk = tr.make_bucket(caps)
         assert bk.batch.x.dim() == 1 and bk.batch.x.dtype == torch.int64
+        o = tr.opt
+        before = [t.clone() for t in (o.flat_p, o.m, o.v, o.step_dev, tr.loss_acc)]
         tr.capture_bucket(bk, BK.pack_raw_z(hb[0], caps, ys[0]))
+        for t, t0 in zip((o.flat_p, o.m, o.v, o.step_dev, tr.loss_acc), before):       # capturing trains nothing
+            assert torch.equal(t, t0)
         losses = []
         for b, y in zip(hb[1:9], ys[1:9]):
             losses.append(tr.step_stream(bk, b, y).clone())

@@ -8,6 +8,7 @@ from moleculesde_amd.geom3d import sde_2d_to_3d as M
 from moleculesde_amd.batch import Batch
 from moleculesde_amd.synthetic import make_batch, make_molecule
 from moleculesde_amd import slabs  # noqa: E402
+from moleculesde_amd.capture import CaptureSession  # noqa: E402
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 
@@ -80,14 +81,8 @@ def case_bwd(name, cpu_b):
             slabs.finish_param_grad_batch()
         for _ in range(3):
             step()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            slabs.new_param_grad_slot(dev)
-            with torch.cuda.graph(g, stream=s):
-                step()
+        with CaptureSession(None, dev, grad_slot=True) as session, session.graph() as g:
+            step()
         res[mol] = timeit(g.replay, 50)
     M.MOL_KERNEL_TRAIN = False
     print(f"{name}: fwd+bwd+weight-gradient reduction in a graph: mol kernels {res[True]:.1f} us, operator path {res[False]:.1f} us")

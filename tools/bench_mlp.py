@@ -8,6 +8,7 @@ from moleculesde_amd import hip
 from moleculesde_amd.geom3d import prepare_batch, nn as _nn
 from moleculesde_amd.synthetic import make_batch
 from moleculesde_amd import slabs  # noqa: E402
+from moleculesde_amd.capture import CaptureSession  # noqa: E402
 
 dev = torch.device("cuda", 0)
 b = prepare_batch(make_batch(256, seed=0), dev)
@@ -41,13 +42,8 @@ def step(fn):
 for name, fn in (("operator chain", chain), ("fused", fused)):
     for _ in range(3):
         step(fn)
-    torch.cuda.synchronize()
-    slabs.new_param_grad_slot(dev)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
+    with CaptureSession(None, dev, grad_slot=True) as session, session.graph() as g:
         step(fn)
-    slabs.flush_table_uploads()
-    slabs.use_eager_param_grad_slot()
     for _ in range(5):
         g.replay()
     torch.cuda.synchronize()

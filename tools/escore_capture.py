@@ -5,6 +5,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import test_gpu_escore as T
 from moleculesde_amd import hip
 from moleculesde_amd import slabs  # noqa: E402
+from moleculesde_amd.capture import CaptureSession  # noqa: E402
 dev = torch.device("cuda", 0)
 M_ = __import__("moleculesde_amd.geom3d.sde_2d_to_3d", fromlist=["x"]); M_.MOL_KERNEL_TRAIN = True
 cpu_b, pl, ep, net, x, ea, basis = T._case(dev, int(sys.argv[1]) if len(sys.argv) > 1 else 16, 3)
@@ -25,14 +26,8 @@ for _ in range(3):
     step()
 torch.cuda.synchronize()
 print("eager ok", float(xd.grad.abs().sum()))
-g = torch.cuda.CUDAGraph()
-s = torch.cuda.Stream()
-s.wait_stream(torch.cuda.current_stream())
-with torch.cuda.stream(s):
-    if mode == "batch":
-        slabs.new_param_grad_slot(dev)
-    with torch.cuda.graph(g, stream=s):
-        step()
+with CaptureSession(None, dev, grad_slot=mode == "batch") as session, session.graph() as g:
+    step()
 print("captured")
 g.replay(); torch.cuda.synchronize()
 print("replayed", float(xd.grad.abs().sum()))

@@ -92,8 +92,7 @@ for use_graph in (True,):
     same_params(tr_1, tr_dp)
     tr_dp.opt.m.zero_(); tr_dp.opt.v.zero_(); tr_dp.opt.step_dev.zero_()
     for it in range(3):
-        g, held, with_adam = tr_dp._graphs[id(shards[rank])]
-        g.replay()
+        tr_dp._graphs[id(shards[rank])].graph.replay()
         torch.cuda.synchronize()
         local = tr_dp.opt.flat_g.clone()
         # eager gradient of MY shard with the reference trainer (same parameters)

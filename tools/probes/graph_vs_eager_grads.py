@@ -42,8 +42,8 @@ tr.step(b)
 tr.capture(b)
 names = {id(p): f"{k}.{n}" for k, m in tr.models.items() for n, p in m.named_parameters()}
 for it in range(2):
-    g, held, with_adam = tr._graphs[id(b)]
-    g.replay()
+    rec = tr._graphs[id(b)]
+    rec.graph.replay()
     torch.cuda.synchronize()
     gg = tr.opt.flat_g.clone()
     loss, _ = tr.losses(b)
@@ -56,7 +56,7 @@ for it in range(2):
         a, c = gg[o:o + sz].double(), ge[o:o + sz].double()
         worst.append((float((a - c).norm()) / max(float(c.norm()), 1e-12), float(c.norm()), names[id(p)]))
     worst.sort(reverse=True)
-    print("iteration", it, "graph loss", float(tr._graph_loss[id(b)]), "eager loss", float(loss))
+    print("iteration", it, "graph loss", float(rec.loss), "eager loss", float(loss))
     for w in worst[:12]:
         print("   rel %.3e  |g| %.3e  %s" % w)
     tr.opt.step()

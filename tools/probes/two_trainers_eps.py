@@ -43,8 +43,7 @@ def eager(tr):
 
 
 for it in range(2):
-    g, _, _ = A._graphs[id(b)]
-    g.replay(); torch.cuda.synchronize()
+    A._graphs[id(b)].graph.replay(); torch.cuda.synchronize()
     ga = A.opt.flat_g.clone()
     gb = eager(B); torch.cuda.synchronize()
     ga2 = eager(A); torch.cuda.synchronize()
