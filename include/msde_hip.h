@@ -877,6 +877,23 @@ int msde_pc_corrector(const float* out, const float* pos, const float* noise, co
                       unsigned long long seed, int n, float snr, float scale_eps, float* x, float* x_mean, void* stream);
 int msde_pc_predictor(const float* out, const float* pos, const float* noise, const float* par, const long long* step,
                       unsigned long long seed, int n, float* x, float* x_mean, void* stream);
+/* The same arithmetic for G molecules sharing one trajectory (the test-set loop of pretrain_MoleculeSDE_inference_2D_to_3D_VE_VP.py
+ * :42-89 generate_samples_from_testset, one launch instead of one trajectory per molecule): group g = the replicas of one
+ * molecule = atoms [group_ptr[g], group_ptr[g + 1]) of the n (group_ptr [G + 1] device int32, increasing from 0 to n; a group
+ * outside 0 <= a < b <= n is skipped).  One workgroup per group and nothing crosses groups: the corrector's mean norms are taken
+ * over the group, in the order msde_pc_corrector uses on the group alone (max_group_atoms: the largest group, sizes the launch);
+ * step [G] (device int64, may be NULL = row 0) is ONE iteration counter PER GROUP, read and advanced by its group's workgroup
+ * only (corrector: row step[g], then step[g] += 1; predictor: row step[g] - 1), so no word is shared inside a launch;
+ * noise [n, 3] is read at the global element, noise == NULL draws (group_seed[g], row, corrector / predictor, element counted
+ * from the group's first atom) = what msde_pc_corrector / msde_pc_predictor draw for that group alone with seed = group_seed[g]
+ * (group_seed [G] on the device; may be NULL when noise is given).  group_bad [G] (device int32, zeroed by the caller, sticky):
+ * set to 1 by the predictor when an x_mean of the group is not finite. */
+int msde_pc_corrector_grouped(const float* out, const float* pos, const float* noise, const float* par, long long* step,
+                              const unsigned long long* group_seed, const int* group_ptr, int G, int n, int max_group_atoms,
+                              float snr, float scale_eps, float* x, float* x_mean, void* stream);
+int msde_pc_predictor_grouped(const float* out, const float* pos, const float* noise, const float* par, const long long* step,
+                              const unsigned long long* group_seed, const int* group_ptr, int G, int n, float* x, float* x_mean,
+                              int* group_bad, void* stream);
 /* MD17 force fine-tuning losses (finetune_MD17.py:68-74): loss[0] = ce mean_b |E_b - y_b| + cf mean |fsign dE - f| over the n3 = 3 N
  * force components (fsign = -1: forces are minus the coordinate gradient dE), and the seeds of the backward pass in the same
  * launch: gE [B] = d loss / d E, gdE [n3] = d loss / d (dE) (|x|' = sign x, 0 at 0, as torch).  One workgroup, fixed order. */

@@ -165,6 +165,8 @@ SIGNATURES = {
     "msde_mul_add_bwd": [P, P, P, LL, P, P, P],
     "msde_pc_corrector": [P, P, P, P, P, ULL, I, F, F, P, P, P],
     "msde_pc_predictor": [P, P, P, P, P, ULL, I, P, P, P],
+    "msde_pc_corrector_grouped": [P, P, P, P, P, P, P, I, I, I, F, F, P, P, P],
+    "msde_pc_predictor_grouped": [P, P, P, P, P, P, P, I, I, P, P, P, P],
     "msde_l1_energy_force_loss": [P, P, I, P, P, I, F, F, F, P, P, P, P],
     "msde_l1_energy_force_loss_acc": [P, P, I, P, P, I, F, F, F, P, P, P, P, P],
     "msde_md17_eval_accumulate": [P, P, I, P, P, I, P, P],

@@ -794,6 +794,112 @@ extern "C" int msde_pc_predictor(const float* out, const float* pos, const float
   return 0;
 }
 
+// ---- grouped predictor-corrector update: many molecules advance through ONE trajectory (sampler.position_PC_generation_grouped).
+// A group = the num_repeat replicas of one molecule = the atoms [group_ptr[g], group_ptr[g + 1]) (contiguous); one workgroup per
+// group, and NOTHING crosses groups: the corrector's mean norms, the noise and the iteration counter are per group, so a molecule
+// walks the trajectory it would walk alone whatever shares its launch.
+//   reduction: the arithmetic and the order of pc_corrector_kernel on the group -- `bs` threads accumulate with stride bs, bs as
+//     msde_pc_corrector picks it from the atom count (the launch is as wide as the largest group needs; the threads past bs add
+//     0.f wave partials behind the active ones, which leaves the sum's bits alone);
+//   noise: noise != NULL is read at the GLOBAL element; noise == NULL draws (group_seed[g], row, stream, element LOCAL to the
+//     group) -- what msde_pc_corrector / _predictor draw for the group alone with seed = group_seed[g];
+//   iteration counter: step [G] int64, ONE COUNTER PER GROUP.  Workgroup g alone reads and writes step[g] (the corrector uses row
+//     step[g] and then advances it, behind the block sums' barriers; the predictor of the same iteration -- a later launch on the
+//     stream -- uses step[g] - 1).  No word is shared between workgroups of a launch, so there is no race, no atomic and no
+//     dispatch-order assumption, nothing to reset between replays, and any number of iterations may share a captured graph.
+//   group_bad [G] (sticky, zeroed by the caller): the predictor sets it when an x_mean of the group is not finite.
+// A group whose bounds are not 0 <= a < b <= n is skipped (the host wrapper refuses such tables; this keeps a bad one in bounds).
+__global__ void __launch_bounds__(1024)
+pc_corrector_grouped_kernel(const float* __restrict__ out, const float* __restrict__ pos, const float* __restrict__ noise,
+                            const float* __restrict__ par_all, long long* __restrict__ step,
+                            const unsigned long long* __restrict__ group_seed, const int* __restrict__ group_ptr, int n, float snr,
+                            float scale_eps, float* __restrict__ x, float* __restrict__ x_mean) {
+  __shared__ float red[16];
+  const int g = blockIdx.x;
+  const int a = group_ptr[g], b = group_ptr[g + 1];
+  if (a < 0 || b > n || b <= a) return;                  // (uniform over the workgroup)
+  const int ng = b - a;
+  const int bs = min((int)blockDim.x, ng >= 512 ? 1024 : 256);
+  const bool live = (int)threadIdx.x < bs;
+  const long long row = step ? step[g] : 0;
+  const float* par = par_all + 4 * row;
+  const float inv_std = 1.f / par[0], alpha = par[2];
+  const unsigned long long seed = noise ? 0ull : group_seed[g];
+  const float* og = out + 3ll * a;
+  const float* nz = noise ? noise + 3ll * a : nullptr;
+  float gs = 0.f, ns = 0.f;
+  if (live)
+    for (int i = threadIdx.x; i < ng; i += bs) {
+      const float g0 = -og[3 * i] * inv_std, g1 = -og[3 * i + 1] * inv_std, g2 = -og[3 * i + 2] * inv_std;
+      const float z0 = pc_draw(nz, seed, row, 0, 3 * i, 3 * ng), z1 = pc_draw(nz, seed, row, 0, 3 * i + 1, 3 * ng),
+                  z2 = pc_draw(nz, seed, row, 0, 3 * i + 2, 3 * ng);
+      gs += sqrtf(g0 * g0 + g1 * g1 + g2 * g2);
+      ns += sqrtf(z0 * z0 + z1 * z1 + z2 * z2);
+    }
+  const float gn = pc_block_sum(gs, red) / (float)ng;
+  const float nn = pc_block_sum(ns, red) / (float)ng;
+  const float r = snr * nn / gn;
+  const float stp = r * r * 2.f * alpha;
+  const float ns2 = sqrtf(stp * 2.f) * scale_eps;
+  if (live)
+    for (int i = threadIdx.x; i < 3 * ng; i += bs) {
+      const float sc = -og[i] * inv_std;
+      const float m = fmaf(stp, sc, pos[3ll * a + i]);
+      x_mean[3ll * a + i] = m;
+      x[3ll * a + i] = fmaf(ns2, pc_draw(nz, seed, row, 0, i, 3 * ng), m);
+    }
+  if (step && threadIdx.x == 0) step[g] = row + 1;       // (every thread read `row` before the block sums' barriers)
+}
+
+__global__ void __launch_bounds__(256)
+pc_predictor_grouped_kernel(const float* __restrict__ out, const float* __restrict__ pos, const float* __restrict__ noise,
+                            const float* __restrict__ par_all, const long long* __restrict__ step,
+                            const unsigned long long* __restrict__ group_seed, const int* __restrict__ group_ptr, int n,
+                            float* __restrict__ x, float* __restrict__ x_mean, int* __restrict__ group_bad) {
+  const int g = blockIdx.x;
+  const int a = group_ptr[g], b = group_ptr[g + 1];
+  if (a < 0 || b > n || b <= a) return;
+  const int ng = b - a;
+  const long long row = step ? step[g] - 1 : 0;
+  const float* par = par_all + 4 * row;
+  const float inv_std = 1.f / par[0], G = par[1], fa = par[3];
+  const float g2 = G * G;
+  const unsigned long long seed = noise ? 0ull : group_seed[g];
+  const float* nz = noise ? noise + 3ll * a : nullptr;
+  bool bad = false;
+  for (int i = threadIdx.x; i < 3 * ng; i += blockDim.x) {
+    const long long e = 3ll * a + i;
+    const float score = -out[e] * inv_std;
+    const float p = pos[e];
+    const float m = p - ((fa - 1.f) * p - g2 * score);        // x - (f - G^2 score)
+    x_mean[e] = m;
+    x[e] = fmaf(G, pc_draw(nz, seed, row, 1, i, 3 * ng), m);
+    bad |= !isfinite(m);
+  }
+  if (bad) group_bad[g] = 1;                               // (every writer stores the same value)
+}
+
+extern "C" int msde_pc_corrector_grouped(const float* out, const float* pos, const float* noise, const float* par, long long* step,
+                                         const unsigned long long* group_seed, const int* group_ptr, int G, int n,
+                                         int max_group_atoms, float snr, float scale_eps, float* x, float* x_mean, void* stream) {
+  if (G <= 0 || n <= 0 || !out || !pos || !par || !group_ptr || !x || !x_mean || (!noise && !group_seed)) return MSDE_EINVAL;
+  MSDE_LAUNCH(pc_corrector_grouped_kernel, dim3(G), dim3(max_group_atoms >= 512 ? 1024 : 256), 0, as_stream(stream), out, pos,
+              noise, par, step, group_seed, group_ptr, n, snr, scale_eps, x, x_mean);
+  MSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int msde_pc_predictor_grouped(const float* out, const float* pos, const float* noise, const float* par,
+                                         const long long* step, const unsigned long long* group_seed, const int* group_ptr, int G,
+                                         int n, float* x, float* x_mean, int* group_bad, void* stream) {
+  if (G <= 0 || n <= 0 || !out || !pos || !par || !group_ptr || !x || !x_mean || !group_bad || (!noise && !group_seed))
+    return MSDE_EINVAL;
+  MSDE_LAUNCH(pc_predictor_grouped_kernel, dim3(G), dim3(256), 0, as_stream(stream), out, pos, noise, par, step, group_seed,
+              group_ptr, n, x, x_mean, group_bad);
+  MSDE_CHECK_LAUNCH();
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ MD17 losses
 // loss = ce mean_b |E_b - y_b| + cf mean_{i,k} |F_ik - f_ik| with F = fsign * dE (finetune_MD17.py:68-74: fsign = -1, the forces are
 // minus the coordinate gradient) and, in the same launch, d loss / d E and d loss / d (dE) -- the seeds of the backward pass
