@@ -1050,6 +1050,26 @@ int msde_l1_energy_force_loss_acc(const float* E, const float* y, int B, const f
 int msde_md17_gather_batch(const float* pos, const float* y, const float* force, int M, int row, const int* perm, int* counter,
                            int stride, int B, float* pos_dst, float* y_dst, float* f_dst, void* stream);
 
+/* ------------------------------------------------------------------ resident dataset ------- */
+/* Geom3D/datasets/dataset_3D.py:106-124 (Molecule3DDataset.get: slice the collated arrays, centre the coordinates) and the
+ * loader's collate, for batch k = counter[0] of an epoch over a molecule store held on the device: x [n_atoms, 9], pos
+ * [n_atoms, 3] (not centred), edge_index [2, n_bonds] (molecule-local, directed, stored order), edge_attr [n_bonds, 3],
+ * atom_ptr / bond_ptr [M + 1] (int64).  The batch holds the molecules perm[k * B + r], r < B (perm: int32 [n_avail], the
+ * epoch's order), written into `blob` (int32 [total_words], 16-byte aligned) in the layout of moleculesde_amd/bucket.py
+ * raw_layout / pack_raw: the field offsets off_* (words, multiples of 4, in this order, off_x == 0) and the capacities cap_N /
+ * cap_Eb / B; bond endpoints become batch-global atom indices; with remove_center the per-molecule mean (summed in atom
+ * order in fp64, divided in fp64, rounded to fp32) is subtracted in fp32.  EVERY word of the blob is written (zero past the
+ * batch's true rows), by kernel stores.  All or nothing: if a perm entry lies outside [0, M) (bit 1 of err[0]), a molecule is
+ * empty or has more than n_max atoms (2), the batch's atoms or bonds exceed cap_N / cap_Eb (4) or fewer than B molecules
+ * remain, (k + 1) * B > n_avail (8), the blob is left as it was and the bits are OR-ed into err[0] (never cleared here).
+ * Prefix sums over the B <= 1024 sizes in fixed order, no atomics: bitwise repeatable.  Then counter[0] = k + 1, in a
+ * one-thread launch behind the gather (in either case). */
+int msde_dataset_gather_batch(const int* x, const float* pos, const int* edge_index, const int* edge_attr,
+                              const long long* atom_ptr, const long long* bond_ptr, long long M, long long n_atoms,
+                              long long n_bonds, const int* perm, int* counter, long long n_avail, int B, int cap_N, int cap_Eb,
+                              int n_max, int remove_center, int off_x, int off_pos, int off_src, int off_dst, int off_attr,
+                              int off_atoms, int off_bonds, int total_words, int* blob, int* err, void* stream);
+
 /* ------------------------------------------------------------------ optimiser -------------- */
 /* torch.optim.Adam step over a flat parameter buffer with per-element lr via segment table —
  * examples/pretrain_MoleculeSDE.py:331-337,156.  seg_end[S] (exclusive ends), seg_lr[S].

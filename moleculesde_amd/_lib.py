@@ -171,6 +171,7 @@ SIGNATURES = {
     "msde_l1_energy_force_loss_acc": [P, P, I, P, P, I, F, F, F, P, P, P, P, P],
     "msde_md17_eval_accumulate": [P, P, I, P, P, I, P, P],
     "msde_md17_gather_batch": [P, P, P, I, I, P, P, I, I, P, P, P, P],
+    "msde_dataset_gather_batch": [P, P, P, P, P, P, LL, LL, LL, P, P, LL, I, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P],
     "msde_randperm": [I, I, ULL, P, P, P, P],
     "msde_ve_perturb": [P, P, P, P, I, I, I, F, F, F, P, P, P],
     "msde_ve_perturb_rng": [P, P, I, I, I, F, F, F, ULL, P, P, P, P, P],

@@ -1,0 +1,436 @@
+"""Pretraining on a user's own molecules at graph-replay speed: a flat molecule store, held in device memory, that feeds
+the captured capacity-bucket step (moleculesde_amd/bucket.py) with no per-batch host work.
+
+The reference does this work once per sample in Molecule3DDataset.get (Geom3D/datasets/dataset_3D.py:106-124: slice the
+collated arrays, extend_graph, subtract the centre) and lets DataLoader(shuffle=True) collate.  Here:
+  * `MoleculeStore` (host): the collated arrays of the whole dataset, molecule-local bond indices, int64 pointer tables, and
+    the extended-edge count of every molecule (what sizes the capacities);
+  * `EpochPlan` (host, numpy): the permutation of one epoch, this rank's shard, and per batch exactly what
+    bucket.raw_sizes would find on the collated batch -- cumulative sums over the permuted per-molecule arrays;
+  * `ResidentDataset`: the store's arrays on the device, the epoch's permutation in a static buffer, a device batch counter,
+    and csrc/dataset.hip (msde_dataset_gather_batch), which writes the raw blob of batch `counter` straight into Bucket.raw
+    -- centring included -- in the layout and conventions of bucket.pack_raw, bit for bit;
+  * `DatasetRunner`: the counterpart of pretrain.StreamRunner -- ONE captured graph {gather, plans, forward, backward, Adam};
+    an epoch is a loop of replays.  Batches outside the capacities (the short last batch, a molecule of more than 32 atoms)
+    take the exact-size eager step on a host-built plan.
+Sub-graph masking (--SSL_masking_ratio; the reference applies it in front of the centring) is not built: its place is a
+per-molecule keep mask read by the gather before the centre is formed.
+"""
+import numpy as np
+import torch
+
+from . import _lib, bucket as BK, plan as _plan
+from ._torchabi import _p, _stream
+from .batch import Batch, MolData, extend_graph_index
+
+FORMAT_VERSION = 1
+_FIELDS = ("x", "positions", "edge_index", "edge_attr", "atom_ptr", "bond_ptr", "ext_count")
+# bits of the gather's error word (csrc/dataset.hip)
+GATHER_ERRORS = {1: "a permutation entry outside [0, M)", 2: "a molecule of more atoms than n_max (or none)",
+                 4: "the batch's atoms or bonds exceed the capacity", 8: "fewer than B molecules remain in the epoch"}
+
+
+def _ext_counts(edge_index, atom_ptr, bond_ptr):
+    """Extended edges per molecule (batch.extend_graph_index: ordered pairs within <= 4 bonds), molecules of one size at a
+    time as batched boolean matrix powers."""
+    n = np.diff(atom_ptr)
+    M = len(n)
+    out = np.zeros(M, dtype=np.int32)
+    bmol = np.repeat(np.arange(M), np.diff(bond_ptr))
+    for size in np.unique(n):
+        size = int(size)
+        if size < 2:
+            continue
+        ids = np.nonzero(n == size)[0]
+        slot = np.full(M, -1, dtype=np.int64)
+        step = max(1, (1 << 22) // (size * size))
+        for lo in range(0, len(ids), step):
+            grp = ids[lo:lo + step]
+            slot[:] = -1
+            slot[grp] = np.arange(len(grp))
+            sel = slot[bmol] >= 0
+            A = np.zeros((len(grp), size, size), dtype=bool)
+            A[slot[bmol[sel]], edge_index[0, sel], edge_index[1, sel]] = True
+            eye = np.eye(size, dtype=bool)[None]
+            for _ in range(2):
+                Pw = np.matmul(A.astype(np.float32), A.astype(np.float32)) > 0
+                A = A | (Pw & ~eye)
+            out[grp] = A.reshape(len(grp), -1).sum(1)
+    return out
+
+
+class MoleculeStore:
+    """A dataset as flat arrays: x [N, 9] int32, positions [N, 3] float32 (NOT centred), edge_index [2, E] int32
+    (molecule-local, directed, stored order), edge_attr [E, 3] int32, atom_ptr / bond_ptr [M + 1] int64, ext_count [M] int32."""
+
+    def __init__(self, x, positions, edge_index, edge_attr, atom_ptr, bond_ptr, ext_count=None):
+        t = torch.as_tensor
+        self.x = t(x).to(torch.int32).reshape(-1, BK.K_ATOM).contiguous()
+        self.positions = t(positions).to(torch.float32).reshape(-1, 3).contiguous()
+        self.edge_index = t(edge_index).to(torch.int32).reshape(2, -1).contiguous()
+        self.edge_attr = t(edge_attr).to(torch.int32).reshape(-1, 3).contiguous()
+        self.atom_ptr = t(atom_ptr).to(torch.int64).reshape(-1).contiguous()
+        self.bond_ptr = t(bond_ptr).to(torch.int64).reshape(-1).contiguous()
+        self._validate()
+        if ext_count is None:
+            ext_count = _ext_counts(self.edge_index.numpy(), self.atom_ptr.numpy(), self.bond_ptr.numpy())
+        self.ext_count = t(ext_count).to(torch.int32).reshape(-1).contiguous()
+        if self.ext_count.numel() != len(self):
+            raise ValueError(f"ext_count holds {self.ext_count.numel()} entries for {len(self)} molecules")
+
+    def __len__(self):
+        return self.atom_ptr.numel() - 1
+
+    # -- validation ------------------------------------------------------------------------------------------------
+    def _validate(self):
+        ap, bp = self.atom_ptr.numpy(), self.bond_ptr.numpy()
+        N, E = self.x.size(0), self.edge_index.size(1)
+        if len(ap) < 2 or len(ap) != len(bp):
+            raise ValueError(f"pointer tables of {len(ap)} and {len(bp)} entries: both hold molecules + 1, at least 2")
+        if self.positions.size(0) != N or self.edge_attr.size(0) != E:
+            raise ValueError(f"x {N} rows vs positions {self.positions.size(0)}; edge_index {E} columns vs edge_attr "
+                             f"{self.edge_attr.size(0)} rows")
+        for name, ptr, total in (("atom_ptr", ap, N), ("bond_ptr", bp, E)):
+            d = np.diff(ptr)
+            if (d < 0).any():
+                raise ValueError(f"{name} is not monotone at molecule {int(np.nonzero(d < 0)[0][0])}")
+            if ptr[0] != 0 or ptr[-1] != total:
+                raise ValueError(f"{name} spans [{int(ptr[0])}, {int(ptr[-1])}], the arrays hold {total} rows")
+        n = np.diff(ap)
+        if (n == 0).any():
+            raise ValueError(f"molecule {int(np.nonzero(n == 0)[0][0])} is empty")
+        mol_of_atom = lambda rows: int(np.searchsorted(ap, rows[0], side="right") - 1)
+        x = self.x.numpy()
+        bad = ((x < 0) | (x >= np.asarray(_plan.ATOM_FEATURE_DIMS)[None])).any(1)
+        if bad.any():
+            raise ValueError(f"molecule {mol_of_atom(np.nonzero(bad)[0])}: an atom feature code outside "
+                             f"{_plan.ATOM_FEATURE_DIMS}")
+        pos = self.positions.numpy()
+        bad = ~np.isfinite(pos).all(1)
+        if bad.any():
+            raise ValueError(f"molecule {mol_of_atom(np.nonzero(bad)[0])}: a coordinate that is not finite")
+        mol_of_bond = lambda rows: int(np.searchsorted(bp, rows[0], side="right") - 1)
+        ea = self.edge_attr.numpy()
+        bad = ((ea < 0) | (ea >= np.asarray(_plan.BOND_FEATURE_DIMS)[None])).any(1)
+        if bad.any():
+            raise ValueError(f"molecule {mol_of_bond(np.nonzero(bad)[0])}: a bond feature code outside "
+                             f"{_plan.BOND_FEATURE_DIMS}")
+        ei = self.edge_index.numpy()
+        n_of_bond = np.repeat(n, np.diff(bp))
+        bad = ((ei < 0) | (ei >= n_of_bond[None])).any(0)
+        if bad.any():
+            raise ValueError(f"molecule {mol_of_bond(np.nonzero(bad)[0])}: a bond endpoint outside the molecule")
+
+    # -- constructors and I/O --------------------------------------------------------------------------------------
+    @staticmethod
+    def from_molecules(mols):
+        """From MolData-like objects (x [n, 9], edge_index [2, e] molecule-local, edge_attr [e, 3], positions [n, 3])."""
+        mols = list(mols)
+        if not mols:
+            raise ValueError("no molecules")
+        for i, m in enumerate(mols):
+            if m.x.dim() != 2 or m.x.size(0) == 0:
+                raise ValueError(f"molecule {i} is empty" if m.x.numel() == 0 else f"molecule {i}: x is not [n, {BK.K_ATOM}]")
+        cat = lambda ts, d: torch.cat([torch.as_tensor(v) for v in ts], dim=d)
+        na = torch.tensor([m.x.size(0) for m in mols], dtype=torch.int64)
+        nb = torch.tensor([m.edge_index.reshape(2, -1).size(1) for m in mols], dtype=torch.int64)
+        zero = torch.zeros(1, dtype=torch.int64)
+        return MoleculeStore(cat([m.x for m in mols], 0), cat([m.positions for m in mols], 0),
+                             cat([m.edge_index.reshape(2, -1) for m in mols], 1),
+                             cat([m.edge_attr.reshape(-1, 3) for m in mols], 0),
+                             torch.cat([zero, na.cumsum(0)]), torch.cat([zero, nb.cumsum(0)]))
+
+    @staticmethod
+    def from_collated(data, slices):
+        """From the two mappings of an InMemoryDataset's processed file (`geometric_data_processed.pt`: collated tensors and
+        their per-key slice tables), read duck-typed: x, edge_index (molecule-local, as InMemoryDataset stores it),
+        edge_attr, positions."""
+        for k in ("x", "edge_index", "edge_attr", "positions"):
+            if k not in data or k not in slices:
+                raise ValueError(f"the collated pair has no '{k}'")
+        ap, bp = torch.as_tensor(slices["x"]).to(torch.int64), torch.as_tensor(slices["edge_index"]).to(torch.int64)
+        if not torch.equal(torch.as_tensor(slices["positions"]).to(torch.int64), ap):
+            raise ValueError("slices['positions'] differs from slices['x']")
+        if not torch.equal(torch.as_tensor(slices["edge_attr"]).to(torch.int64), bp):
+            raise ValueError("slices['edge_attr'] differs from slices['edge_index']")
+        return MoleculeStore(data["x"], data["positions"], data["edge_index"], data["edge_attr"], ap, bp)
+
+    def save(self, path):
+        d = {k: getattr(self, k) for k in _FIELDS}
+        d["format_version"] = FORMAT_VERSION
+        torch.save(d, path)
+
+    @staticmethod
+    def load(path):
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        if d.get("format_version") != FORMAT_VERSION:
+            raise ValueError(f"{path}: format version {d.get('format_version')}, this build reads {FORMAT_VERSION}")
+        return MoleculeStore(*(d[k] for k in _FIELDS))
+
+    # -- per-molecule views ------------------------------------------------------------------------------------------
+    def _span(self, i):
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise IndexError(f"molecule {i} of {len(self)}")
+        return (int(self.atom_ptr[i]), int(self.atom_ptr[i + 1]), int(self.bond_ptr[i]), int(self.bond_ptr[i + 1]))
+
+    def centred_positions(self, i):
+        """dataset_3D.py:120-122 with the arithmetic of csrc/dataset.hip, so that the two agree bit for bit: per axis the
+        coordinates are summed in atom order in fp64, divided by n in fp64, rounded to fp32 and subtracted in fp32."""
+        a0, a1, _, _ = self._span(i)
+        p = self.positions[a0:a1].numpy()
+        s = np.zeros(3, dtype=np.float64)
+        for row in p:                           # (sequential on purpose: numpy's own sum is pairwise)
+            s = s + row.astype(np.float64)
+        centre = (s / np.float64(a1 - a0)).astype(np.float32)
+        return torch.from_numpy(p - centre[None])
+
+    def molecule(self, i, remove_center=False, extended=False):
+        """Molecule i as a MolData with int64 fields, as the models and Batch.from_data_list expect; `extended` attaches
+        extended_edge_index (dataset_3D.py:116-118), `remove_center` the centred coordinates."""
+        a0, a1, b0, b1 = self._span(i)
+        ei = self.edge_index[:, b0:b1].to(torch.int64)
+        d = MolData(x=self.x[a0:a1].to(torch.int64), edge_index=ei, edge_attr=self.edge_attr[b0:b1].to(torch.int64),
+                    positions=self.centred_positions(i) if remove_center else self.positions[a0:a1].clone())
+        if extended:
+            d.extended_edge_index = extend_graph_index(ei, a1 - a0)
+        return d
+
+    def collate(self, indices, remove_center=True):
+        """The host batch of these molecules, in this order (what the reference's loader would collate)."""
+        return Batch.from_data_list([self.molecule(int(i), remove_center=remove_center, extended=True) for i in indices])
+
+    def epoch_plan(self, epoch, batch_size, shuffle=True, seed=0, rank=0, world=1, perm=None):
+        return EpochPlan(self, epoch, batch_size, shuffle=shuffle, seed=seed, rank=rank, world=world, perm=perm)
+
+
+class EpochPlan:
+    """One epoch on one rank, host only.  The permutation comes from a CPU torch.Generator seeded by (seed, epoch): the same
+    on every rank; the rank's shard is perm[rank::world] cut to the common length.  `needs[key][k]` is what bucket.raw_sizes
+    finds on the collated batch k (B, N, E_b, E_e from ext_count, E_r = sum n min(n - 1, 32), P = sum n^2, n_max); the short
+    last batch is kept (drop_last=False, the DataLoader default the reference uses)."""
+
+    def __init__(self, store, epoch, batch_size, shuffle=True, seed=0, rank=0, world=1, perm=None):
+        M, B = len(store), int(batch_size)
+        if B < 1 or not 0 <= int(rank) < int(world):
+            raise ValueError(f"batch_size {B}, rank {rank} of {world}")
+        if perm is not None:
+            full = np.asarray(torch.as_tensor(perm).cpu().numpy(), dtype=np.int64).reshape(-1)
+            if len(full) and (full.min() < 0 or full.max() >= M):
+                first = int(np.nonzero((full < 0) | (full >= M))[0][0])
+                raise ValueError(f"permutation entry {first} is {int(full[first])}: outside [0, {M})")
+        elif shuffle:
+            g = torch.Generator().manual_seed((int(seed) * 1000003 + int(epoch)) & 0x7FFFFFFFFFFFFFFF)
+            full = torch.randperm(M, generator=g).numpy()
+        else:
+            full = np.arange(M, dtype=np.int64)
+        self.epoch, self.batch_size, self.rank, self.world = int(epoch), B, int(rank), int(world)
+        self.full_perm = full
+        self.perm = np.ascontiguousarray(full[rank::world][:len(full) // world])
+        L = len(self.perm)
+        if L == 0:
+            raise ValueError(f"{len(full)} molecules over {world} ranks leave this rank none")
+        self.n_batches, self.n_full = -(-L // B), L // B
+        n = np.diff(store.atom_ptr.numpy())[self.perm]
+        per_mol = {"N": n, "E_b": np.diff(store.bond_ptr.numpy())[self.perm], "E_e": store.ext_count.numpy()[self.perm].astype(np.int64),
+                   "E_r": n * np.minimum(np.maximum(n - 1, 0), BK.MAX_NBR), "P": n * n}
+        starts = np.arange(self.n_batches) * B
+        ends = np.minimum(starts + B, L)
+        self.needs = {"B": ends - starts, "n_max": np.maximum.reduceat(n, starts)}
+        for k, v in per_mol.items():
+            c = np.concatenate([[0], np.cumsum(v, dtype=np.int64)])
+            self.needs[k] = c[ends] - c[starts]
+
+    def __len__(self):
+        return self.n_batches
+
+    def need(self, k):
+        return {key: int(v[k]) for key, v in self.needs.items()}
+
+    def molecules(self, k):
+        return self.perm[k * self.batch_size:(k + 1) * self.batch_size]
+
+    def fits(self, caps):
+        """Per batch: does it fit these Caps (bucket.Caps.fits, vectorised)?  The short last batch never does."""
+        nd = self.needs
+        return ((nd["B"] == caps.B) & (nd["N"] <= caps.N) & (nd["E_b"] <= caps.E_b) & (nd["E_e"] <= caps.E_e) &
+                (nd["E_r"] <= caps.E_r) & (nd["P"] <= caps.P) & (nd["n_max"] <= min(caps.n_max, BK.PLAN_NMAX)))
+
+
+def caps_for(plan, n_max=None):
+    """The default capacity rule: Caps.covering over the plan's full batches that csrc/plan.hip can build (molecules of up to
+    PLAN_NMAX atoms; the others take the fallback)."""
+    ks = [k for k in range(plan.n_full) if plan.needs["n_max"][k] <= (n_max or BK.PLAN_NMAX)]
+    if not ks:
+        raise BK.BucketOverflow(f"no full batch of {plan.batch_size} molecules with every molecule within "
+                                f"{n_max or BK.PLAN_NMAX} atoms: nothing for the captured step to run on")
+    return BK.Caps.covering([plan.need(k) for k in ks], n_max=n_max)
+
+
+class ResidentDataset:
+    """The store on the device (uploaded once), the epoch's permutation in a static int32 buffer, the device batch counter
+    and the gather's own error word (Bucket.err is cleared by every msde_plan_build)."""
+
+    def __init__(self, store, device):
+        self.store, self.device = store, torch.device(device)
+        if len(store) >= 2 ** 31:
+            raise ValueError("the permutation buffer is int32")
+        up = lambda t: t.to(self.device).contiguous()
+        self.x, self.pos, self.edge_index, self.edge_attr = up(store.x), up(store.positions), up(store.edge_index), up(store.edge_attr)
+        self.atom_ptr, self.bond_ptr = up(store.atom_ptr), up(store.bond_ptr)
+        self.perm = torch.zeros(len(store), dtype=torch.int32, device=self.device)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.n_avail = 0
+        self._err_host, self._err_event = None, None
+
+    def epoch_plan(self, epoch, batch_size, **kw):
+        return self.store.epoch_plan(epoch, batch_size, **kw)
+
+    def begin_epoch(self, plan):
+        """Per-epoch setup: the permutation into the static buffer (a torch copy) and the counter back to zero, both on the
+        current stream.  The shard length is a launch argument of a captured gather: it may not change under a graph."""
+        L = len(plan.perm)
+        src = torch.from_numpy(plan.perm.astype(np.int32))
+        self.perm[:L].copy_(src.pin_memory() if self.device.type == "cuda" else src, non_blocking=True)
+        self.counter.zero_()
+        self.n_avail = L
+
+    def launch_gather(self, blob, layout, caps, n_max=None, remove_center=True, n_avail=None, perm=None, counter=None, err=None):
+        """msde_dataset_gather_batch on the current stream, unchecked on the host (the kernel's own guards hold): batch
+        `counter[0]` of `perm` into `blob` (int32 [layout['_total']]), then counter[0] += 1."""
+        lay = layout
+        perm = self.perm if perm is None else perm
+        assert perm.dtype == torch.int32 and perm.is_contiguous() and blob.dtype == torch.int32 and blob.is_contiguous()
+        n_avail = self.n_avail if n_avail is None else int(n_avail)
+        if n_avail > perm.numel() or blob.numel() < lay["_total"]:
+            raise ValueError(f"n_avail {n_avail} vs a permutation of {perm.numel()}; blob {blob.numel()} vs {lay['_total']} words")
+        _lib.call("msde_dataset_gather_batch", _p(self.x), _p(self.pos), _p(self.edge_index), _p(self.edge_attr),
+                  _p(self.atom_ptr), _p(self.bond_ptr), len(self.store), self.x.size(0), self.edge_index.size(1), _p(perm),
+                  _p(self.counter if counter is None else counter), n_avail, caps.B, caps.N, caps.E_b,
+                  int(caps.n_max if n_max is None else n_max), int(bool(remove_center)),
+                  *(lay[k][0] for k in ("x", "pos", "bond_src", "bond_dst", "bond_attr", "mol_atoms", "mol_bonds")),
+                  lay["_total"], _p(blob), _p(self.err if err is None else err), _stream())
+
+    def gather(self, bk, plan, k, remove_center=True):
+        """Host-checked gather of batch k of `plan` (after begin_epoch(plan)) into a bucket: refuses, before any launch, a
+        batch the plan marks as not fitting the bucket's capacities."""
+        if not 0 <= k < plan.n_batches or not bool(plan.fits(bk.caps)[k]):
+            raise BK.BucketOverflow(f"batch {k} {plan.need(k) if 0 <= k < plan.n_batches else ''} does not fit the bucket "
+                                    f"{bk.caps.as_dict()}")
+        self.counter.fill_(k)
+        self.launch_gather(bk.raw, bk.layout, bk.caps, remove_center=remove_center)
+
+    def poll_error(self):
+        """The gather's error word WITHOUT a synchronisation (Bucket.poll_overflow's scheme): the word as it was when the
+        previous poll's copy completed, and the next copy queued behind the work submitted so far."""
+        if self._err_host is None:
+            self._err_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        seen = 0
+        if self._err_event is not None:
+            self._err_event.synchronize()
+            seen = int(self._err_host[0])
+        self._err_host.copy_(self.err, non_blocking=True)
+        self._err_event = torch.cuda.Event()
+        self._err_event.record()
+        return seen
+
+
+def describe_error(bits):
+    return "; ".join(v for b, v in GATHER_ERRORS.items() if bits & b) or "none"
+
+
+class DatasetRunner:
+    """pretrain.StreamRunner's surface (ensure_captured / run / fallbacks) on a resident dataset: ONE bucket, ONE captured graph
+    {gather of batch `counter` + device-side plans + forward + backward + Adam}; a step is one replay, nothing is copied
+    from or packed on the host.  run(plan, steps) takes an EpochPlan where StreamRunner.run takes batches."""
+
+    def __init__(self, trainer, resident, plan, caps=None, remove_center=True):
+        from . import pretrain as PT
+        self.PT, self.tr, self.rd, self.remove_center = PT, trainer, resident, bool(remove_center)
+        self.caps = caps or caps_for(plan)
+        trainer.check_bucket_metric()
+        fits = plan.fits(self.caps)
+        if not bool(fits[0]):
+            raise BK.BucketOverflow(f"the first batch {plan.need(0)} does not fit the bucket {self.caps.as_dict()}")
+        self._check_neg_samples(plan)
+        self.bk = bk = trainer.make_bucket(self.caps)
+        self.fallbacks = 0
+        # warm up as Trainer.capture_bucket does: batch 0 gathered eagerly, its plans, two eager steps; then capture
+        resident.begin_epoch(plan)
+        self.n_avail = resident.n_avail
+        self._gather()
+        bk.build_plan_on_device()
+        ok, sizes = bk.check()
+        bits = int(resident.err.cpu())
+        if not ok or bits:
+            raise BK.BucketOverflow(f"batch does not fit the bucket: {sizes} vs {self.caps.as_dict()} (gather: {describe_error(bits)})")
+        for _ in range(2):
+            trainer.step(bk.batch)
+        self._capture()
+
+    def _gather(self):
+        self.rd.launch_gather(self.bk.raw, self.bk.layout, self.caps, remove_center=self.remove_center, n_avail=self.n_avail)
+
+    def _capture(self):
+        tr, PT = self.tr, self.PT
+        side = tr._side_stream if (tr.overlap_streams and PT.PLAN_LISTS_ON_SIDE) else None
+        tr.capture(self.bk.batch, pre=lambda: (self._gather(), self.bk.build_plan_on_device(side)))
+        self._captured_coeffs = (float(tr.coeff_cl),)
+
+    def ensure_captured(self):
+        """The loss coefficients are baked into the graph: after a change (contrastive skip epochs) capture again."""
+        if (float(self.tr.coeff_cl),) != self._captured_coeffs:
+            self.tr.check_bucket_metric()
+            # (the superseded graph is parked, not destroyed: see StreamRunner.ensure_captured)
+            self._parked = getattr(self, "_parked", []) + [self.tr._graphs.pop(id(self.bk.batch), None)]
+            self._capture()
+
+    def _check_neg_samples(self, plan):
+        """EBM_dot_prod: 1 <= K < N (pretrain.check_bucket_neg_samples) for the smallest batch of the epoch, before it starts."""
+        a = self.tr.args
+        if a.CL_similarity_metric == "EBM_dot_prod" and self.tr.coeff_cl > 0:
+            self.PT._neg_samples(a, int(plan.needs["N"].min()))
+
+    def run(self, plan, steps=None):
+        """One epoch (or its first `steps` batches).  Returns the number of steps taken."""
+        n = plan.n_batches if steps is None else min(int(steps), plan.n_batches)
+        if n == 0:
+            return 0
+        if len(plan.perm) != self.n_avail:
+            raise ValueError(f"an epoch of {len(plan.perm)} molecules on a graph captured for {self.n_avail}")
+        fits = plan.fits(self.caps)
+        self._check_neg_samples(plan)
+        rd, bk, tr = self.rd, self.bk, self.tr
+        rd.begin_epoch(plan)
+        for k in range(n):
+            if fits[k]:
+                bits = rd.poll_error()
+                if bits or bk.poll_overflow():
+                    raise BK.BucketOverflow(f"a batch did not fit the bucket {self.caps.as_dict()} (gather: {describe_error(bits)}): "
+                                            "that step is not a valid update")
+                tr.step_graph(bk.batch)
+            else:                               # exact-size eager step on a host-built plan; the device counter moves on
+                self.fallbacks += 1
+                b = rd.store.collate(plan.molecules(k), remove_center=self.remove_center)
+                tr.step(self.PT.prepare_batch(b, tr.device))
+                rd.counter.add_(1)
+        return n
+
+
+class EagerDatasetRunner:
+    """The exact-size loop over host-collated batches of the same epoch plans (pretrain --eager --dataset_file)."""
+    fallbacks = 0
+
+    def __init__(self, trainer, store, remove_center=True):
+        self.tr, self.store, self.remove_center = trainer, store, bool(remove_center)
+
+    def ensure_captured(self):
+        pass
+
+    def run(self, plan, steps=None):
+        from .geom3d import prepare_batch
+        n = plan.n_batches if steps is None else min(int(steps), plan.n_batches)
+        for k in range(n):
+            self.tr.step(prepare_batch(self.store.collate(plan.molecules(k), remove_center=self.remove_center), self.tr.device))
+        return n

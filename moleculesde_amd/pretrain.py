@@ -5,7 +5,8 @@ loss composition  CL*c1 + L_2Dto3D*c2 + 0.5(L_x + L_adj)*c3  (:135-152), same op
 (:331-337), same checkpoint dictionary (:78-88).  Differences, all deliberate:
   * per-step loss logging accumulates on the device (the reference forces 3 D2H syncs per step);
   * Adam is one flat HIP kernel; under DP one RCCL all-reduce precedes it;
-  * the data here is the synthetic PCQM4Mv2-shaped generator (no dataset exists in the containers).
+  * the data is a molecule store held on the device (--dataset_file, moleculesde_amd/dataset.py) or, without one, the
+    synthetic PCQM4Mv2-shaped generator.
 """
 import argparse
 import os
@@ -1048,18 +1049,47 @@ def train_epochs(args, trainer, runner, epoch_items, rank=0, out=print):
     return hist
 
 
-def main(argv=None):
-    """Counterpart of examples/pretrain_MoleculeSDE.py:178-348 on synthetic PCQM4Mv2-shaped data (no dataset in this
-    image): the same flags, models, optimiser groups, epoch report and checkpoints; the batches of an epoch stream through
-    StreamRunner (one captured graph, raw blobs prefetched) -- the mode bench.py's headline measures.  `--eager` keeps the
-    per-kernel host launches on resident batches (the round-1 loop); InfoNCE_dot_prod and EBM_dot_prod take that loop too
-    unless `--captured_cl` is given."""
-    from .synthetic import make_batch
+def main_parser():
+    """The flags of main(): the hot-path flags of examples/config.py plus the loop's own."""
     p = add_hot_path_flags(argparse.ArgumentParser(description=__doc__))
-    p.add_argument("--steps_per_epoch", type=int, default=200)
+    p.add_argument("--steps_per_epoch", type=int, default=None,
+                   help="steps of an epoch (default: 200 on synthetic data, the whole epoch with --dataset_file)")
     p.add_argument("--synthetic_pool", type=int, default=64, help="distinct synthetic batches an epoch cycles over")
     p.add_argument("--eager", action="store_true", help="launch every kernel from the host (no hipGraph, no bucket)")
-    args = p.parse_args(argv)
+    p.add_argument("--dataset_file", type=str, default=None,
+                   help="a dataset.MoleculeStore file: train on it, held on the device (default: synthetic batches)")
+    p.add_argument("--shuffle_seed", type=int, default=0, help="seed of the epoch permutations (--dataset_file)")
+    p.add_argument("--no_shuffle", action="store_true", help="epochs in the store's order (--dataset_file)")
+    p.add_argument("--keep_center", action="store_true",
+                   help="do not subtract each molecule's centre (the reference script passes remove_center=True)")
+    return p
+
+
+def _main_dataset(args, trainer, rank, world):
+    """main() on a molecule store (--dataset_file): the store is uploaded once and every epoch is a loop of graph replays
+    fed by csrc/dataset.hip (dataset.DatasetRunner); under --eager the exact-size loop over host-collated batches of the same
+    epoch plans.  Capacities: dataset.caps_for on epoch 1.  Under data parallelism each rank takes its shard."""
+    from . import dataset as DS
+    store = DS.MoleculeStore.load(args.dataset_file)
+    kw = dict(shuffle=not args.no_shuffle, seed=args.shuffle_seed, rank=rank, world=world)
+    plan_of = lambda epoch: store.epoch_plan(epoch, args.batch_size, **kw)
+    if args.eager:
+        runner = DS.EagerDatasetRunner(trainer, store, remove_center=not args.keep_center)
+    else:
+        runner = DS.DatasetRunner(trainer, DS.ResidentDataset(store, trainer.device), plan_of(1),
+                                  remove_center=not args.keep_center)
+    return train_epochs(args, trainer, runner, lambda e: (plan_of(e), args.steps_per_epoch), rank)
+
+
+def main(argv=None):
+    """Counterpart of examples/pretrain_MoleculeSDE.py:178-348: the same flags, models, optimiser groups, epoch report and
+    checkpoints.  Without --dataset_file the data is synthetic and PCQM4Mv2-shaped: the batches of an epoch stream through
+    StreamRunner (one captured graph, raw blobs prefetched) -- the mode bench.py's headline measures.  With it the models
+    train on that molecule store through dataset.DatasetRunner (_main_dataset).  `--eager` keeps the per-kernel host
+    launches on exact-size batches (the round-1 loop); InfoNCE_dot_prod and EBM_dot_prod take that loop too unless
+    `--captured_cl` is given."""
+    from .synthetic import make_batch
+    args = main_parser().parse_args(argv)
     if not args.eager and args.SDE_coeff_contrastive > 0 and args.CL_similarity_metric not in bucket_cl_metrics(args):
         print(f"CL_similarity_metric={args.CL_similarity_metric}: the captured bucket step takes EBM_node_dot_prod only, "
               "training on resident exact-size batches (--eager); --captured_cl runs this metric in the captured step",
@@ -1070,6 +1100,10 @@ def main(argv=None):
     torch.cuda.set_device(device)
     torch.manual_seed(0)
     trainer = Trainer(args, device)
+    if args.dataset_file:
+        return _main_dataset(args, trainer, rank, world)
+    if args.steps_per_epoch is None:
+        args.steps_per_epoch = 200
     cpu_pool = [make_batch(args.batch_size, seed=dp.shard_seed(s, rank)) for s in range(args.synthetic_pool)]
     if args.eager:
         pool = [prepare_batch(b, device) for b in cpu_pool[:4]]
