@@ -77,6 +77,19 @@ int msde_plan_build(const int* x_raw, int K, const int* atom_off, const int* bon
                     int* b_src, int* b_dst, int* b_rowptr_s, int* b_perm_s, int* bond_codes, float* bond_type,
                     unsigned* ext_rows, int* ext_cnt, int* ext_ptr, int* e_rowptr, int* e_src, int* e_dst,
                     int* e_rowptr_s, int* e_perm_s, int* err, void* stream);
+/* msde_plan_build with the extended rows GIVEN instead of derived from the blob's bonds: ext_rows_in [N_cap], per atom the bit
+ * mask of its extended neighbours in molecule-local numbering.  Geom3D/datasets/dataset_3D.py:95-102,114-118: extend_graph
+ * runs on the whole molecule and `subgraph` then restricts its edges to the kept atoms, so two kept atoms joined only through
+ * a dropped one stay extended neighbours -- which the kept bonds alone cannot tell.  Each row is sanitised before use (bits at
+ * or above the molecule's atom count and the self bit are cleared; *err is set if any were); the extended-edge counts, CSR
+ * views, sizes and tails follow from the sanitised rows exactly as in msde_plan_build.  ext_rows_in == NULL: msde_plan_build. */
+int msde_plan_build_ext(const int* x_raw, int K, const int* atom_off, const int* bond_src, const int* bond_dst,
+                        const int* bond_attr, const int* bond_off, const int* mol_atoms, const int* mol_bonds,
+                        int B, int N_cap, int Eb_cap, int Ee_cap, int P_cap, int Er_cap, int max_nbr, int* mol_ptr,
+                        int* bond_ptr, int* pair_ptr, int* sizes, int* batch_i32, int* atom_codes, int* z_codes, int* b_rowptr,
+                        int* b_src, int* b_dst, int* b_rowptr_s, int* b_perm_s, int* bond_codes, float* bond_type,
+                        unsigned* ext_rows, int* ext_cnt, int* ext_ptr, int* e_rowptr, int* e_src, int* e_dst,
+                        int* e_rowptr_s, int* e_perm_s, int* err, const unsigned* ext_rows_in, void* stream);
 /* Per-table-row atom lists of the embedding backward (msde_embedding_sum_bwd): for codes [*n_dev][K] with values in
  * [0, R): list_ptr [R+1], items = atom index of every entry with that code, in ascending (atom, column) order; cnt [R]
  * is scratch. */
@@ -1069,6 +1082,37 @@ int msde_dataset_gather_batch(const int* x, const float* pos, const int* edge_in
                               long long n_bonds, const int* perm, int* counter, long long n_avail, int B, int cap_N, int cap_Eb,
                               int n_max, int remove_center, int off_x, int off_pos, int off_src, int off_dst, int off_attr,
                               int off_atoms, int off_bonds, int total_words, int* blob, int* err, void* stream);
+/* Sub-graph masking of the resident store (Geom3D/datasets/dataset_3D.py:53-104 `subgraph`, applied at :117-118 between
+ * extend_graph and the centring; examples/config.py --SSL_masking_ratio).
+ *   msde_dataset_ext_rows (dataset_3D.py:12-35 on the WHOLE molecule, once per store): rows [n_atoms], per atom of a molecule
+ *     of <= 32 atoms the bit mask of the atoms within <= 4 bonds (two rounds of A |= A.A minus the diagonal over the stored
+ *     directed bonds, no self bit, molecule-local numbering); atoms of larger molecules get 0.
+ *   msde_dataset_mask_epoch (dataset_3D.py:53-73, once per epoch): keep [M], bit i of keep[m] set = atom i of molecule m is
+ *     kept.  keep_count [33]: atoms to keep of a molecule of n atoms, computed on the host as min(n, int(n * (1 - ratio)) + 1)
+ *     (the `while len(idx_sub) <= sub_num` of :62 keeps sub_num + 1).  Draw d = 0, 1, ... of molecule m takes the 24-bit
+ *     integer u = mix(mix(mask_seed + 0xD1B54A32D192ED69 * (epoch + 1), m), d) >> 40 (mix = the 64-bit mixer of msde_uniform,
+ *     csrc/msde_common.h) and picks member (u * count) >> 24, in ascending atom order, of: all atoms (d = 0); the frontier
+ *     (unkept atoms one stored bond src -> dst from a kept atom) while it is not empty; all unkept atoms otherwise.  Integer
+ *     arithmetic only: moleculesde_amd/dataset.py bfs_keep gives the same words.  Molecules of more than 32 atoms (or with
+ *     pointer tables outside the store) get 0.
+ *   msde_dataset_gather_batch_masked (dataset_3D.py:75-102,120-122 and the loader's collate): msde_dataset_gather_batch of
+ *     the masked molecules.  Kept atoms in ascending order; bonds with both ends kept in stored order with relabelled ends;
+ *     the centre is the mean over the kept atoms (same arithmetic); mol_atoms / mol_bonds and all prefix sums are masked
+ *     counts.  ext_in [cap_N] (every word written): per kept atom its whole-molecule row (mol_rows [n_atoms], from
+ *     msde_dataset_ext_rows) ANDed with the keep word and compressed to the new numbering -- the input of
+ *     msde_plan_build_ext; zero past the batch's atoms.  The same all-or-nothing guards and error bits, plus bit 16: a keep
+ *     word that is zero or has bits at or above the molecule's atom count (molecules of more than 32 atoms: bit 2). */
+int msde_dataset_ext_rows(const int* edge_index, const long long* atom_ptr, const long long* bond_ptr, long long M,
+                          long long n_atoms, long long n_bonds, unsigned* rows, void* stream);
+int msde_dataset_mask_epoch(const int* edge_index, const long long* atom_ptr, const long long* bond_ptr, long long M,
+                            long long n_atoms, long long n_bonds, unsigned long long mask_seed, long long epoch,
+                            const int* keep_count, unsigned* keep, void* stream);
+int msde_dataset_gather_batch_masked(const int* x, const float* pos, const int* edge_index, const int* edge_attr,
+                                     const long long* atom_ptr, const long long* bond_ptr, long long M, long long n_atoms,
+                                     long long n_bonds, const int* perm, int* counter, long long n_avail, int B, int cap_N,
+                                     int cap_Eb, int n_max, int remove_center, int off_x, int off_pos, int off_src, int off_dst,
+                                     int off_attr, int off_atoms, int off_bonds, int total_words, const unsigned* keep,
+                                     const unsigned* mol_rows, int* blob, unsigned* ext_in, int* err, void* stream);
 
 /* ------------------------------------------------------------------ optimiser -------------- */
 /* torch.optim.Adam step over a flat parameter buffer with per-element lr via segment table —

@@ -112,6 +112,7 @@ SIGNATURES = {
     "msde_dense_pc_corrector": [P, P, I, P, P, P, P],
     "msde_dense_pc_predictor": [P, P, I, P, P, P, P],
     "msde_plan_build": [P, I, P, P, P, P, P, P, P, I, I, I, I, I, I, I] + [P] * 23 + [P],
+    "msde_plan_build_ext": [P, I, P, P, P, P, P, P, P, I, I, I, I, I, I, I] + [P] * 23 + [P, P],
     "msde_plan_row_lists": [P, P, I, I, P, P, P, P],
     "msde_dd_unary": [P, P, LL, I, I, F, P, P],
     "msde_dd_unary_mul": [P, P, P, P, LL, I, I, F, P, P],
@@ -172,6 +173,10 @@ SIGNATURES = {
     "msde_md17_eval_accumulate": [P, P, I, P, P, I, P, P],
     "msde_md17_gather_batch": [P, P, P, I, I, P, P, I, I, P, P, P, P],
     "msde_dataset_gather_batch": [P, P, P, P, P, P, LL, LL, LL, P, P, LL, I, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P],
+    "msde_dataset_ext_rows": [P, P, P, LL, LL, LL, P, P],
+    "msde_dataset_mask_epoch": [P, P, P, LL, LL, LL, ULL, LL, P, P, P],
+    "msde_dataset_gather_batch_masked": [P, P, P, P, P, P, LL, LL, LL, P, P, LL, I, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P,
+                                         P, P, P],
     "msde_randperm": [I, I, ULL, P, P, P, P],
     "msde_ve_perturb": [P, P, P, P, I, I, I, F, F, F, P, P, P],
     "msde_ve_perturb_rng": [P, P, I, I, I, F, F, F, ULL, P, P, P, P, P],

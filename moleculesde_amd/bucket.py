@@ -167,10 +167,11 @@ def pack_raw_z(b, caps, y, pin=False):
 
 # ------------------------------------------------------------------------------------------------ the bucket
 class Bucket:
-    def __init__(self, caps, device, atom_dims=None, bond_dims=None, node_class=119, z_only=False):
+    def __init__(self, caps, device, atom_dims=None, bond_dims=None, node_class=119, z_only=False, ext_in=False):
         """z_only: batches with a 1-D atomic number and one target per molecule (pack_raw_z); the plan then holds the
-        atomic-number lists only, and `batch.x` is a 1-D int64 placeholder."""
+        atomic-number lists only, and `batch.x` is a 1-D int64 placeholder.  ext_in: see alloc_ext_in."""
         self.caps, self.device = caps, device
+        self.ext_in = None
         self.z_only = bool(z_only)
         self.k = 1 if z_only else K_ATOM
         atom_dims = list(atom_dims or ([node_class] if z_only else _plan.ATOM_FEATURE_DIMS))
@@ -190,6 +191,8 @@ class Bucket:
         self.sizes, self.err = i32(8), i32(1)
         self.mol_ptr_full, self.bond_ptr, self.pair_ptr = i32(c.B + 2), i32(c.B + 1), i32(c.B + 1)
         self.ext_rows, self.ext_cnt, self.ext_ptr = i32(c.N), i32(c.B), i32(c.B + 1)
+        if ext_in:
+            self.alloc_ext_in()
         pl = types.SimpleNamespace()
         pl.N, pl.B, pl.N_max, pl.max_nbr, pl.E_r_cap = c.N, c.B, c.n_max, MAX_NBR, c.E_r
         pl.err_dev = self.err             # kernels that can detect a capacity overflow of their own raise the bucket's flag
@@ -228,6 +231,15 @@ class Bucket:
         from .geom3d import nn as _nn
         _nn.register_plan(b, pl)
 
+    def alloc_ext_in(self):
+        """The optional input `ext_in` [N] (int32 bit masks, molecule-local): per atom its extended neighbours, GIVEN by the
+        feed instead of derived from the blob's bonds.  While it is set, build_plan_on_device calls msde_plan_build_ext:
+        sub-graph masking (moleculesde_amd/dataset.py) keeps the whole molecule's <= 4-bond pairs among the kept atoms,
+        which the kept bonds alone cannot tell.  Zero rows past the batch's atoms."""
+        if self.ext_in is None:
+            self.ext_in = torch.zeros(self.caps.N, dtype=torch.int32, device=self.device)
+        return self.ext_in
+
     # -- feeding -----------------------------------------------------------------------------------------------
     def load(self, blob):
         """Copy a raw blob (host pinned / pageable, or device) into the bucket: the only per-batch transfer."""
@@ -239,12 +251,13 @@ class Bucket:
         there, behind the CSR build, so the forward of the main chain starts without them; the caller's streams must be
         joined before the backward pass (the trainer's second stream is)."""
         c, pl, p, st = self.caps, self.plan, hip._p, hip._stream()
-        _lib.call("msde_plan_build", p(self.x_raw), self.k, p(self.atom_off), p(self.bond_src_raw), p(self.bond_dst_raw),
-                  p(self.bond_attr_raw), p(self.bond_off), p(self.mol_atoms), p(self.mol_bonds), c.B, c.N, c.E_b, c.E_e,
-                  c.P, c.E_r, MAX_NBR, p(self.mol_ptr_full), p(self.bond_ptr), p(self.pair_ptr), p(self.sizes), p(pl.batch_i32),
+        ext = () if self.ext_in is None else (p(self.ext_in),)
+        _lib.call("msde_plan_build_ext" if ext else "msde_plan_build", p(self.x_raw), self.k, p(self.atom_off),
+                  p(self.bond_src_raw), p(self.bond_dst_raw), p(self.bond_attr_raw), p(self.bond_off), p(self.mol_atoms),
+                  p(self.mol_bonds), c.B, c.N, c.E_b, c.E_e, c.P, c.E_r, MAX_NBR, p(self.mol_ptr_full), p(self.bond_ptr), p(self.pair_ptr), p(self.sizes), p(pl.batch_i32),
                   p(pl.atom_codes), p(pl.z_codes), p(pl.bond.rowptr), p(pl.bond.src), p(pl.bond.dst), p(pl.bond.rowptr_s),
                   p(pl.bond.perm_s), p(pl.bond_codes), p(pl.bond_type), p(self.ext_rows), p(self.ext_cnt), p(self.ext_ptr),
-                  p(pl.ext.rowptr), p(pl.ext.src), p(pl.ext.dst), p(pl.ext.rowptr_s), p(pl.ext.perm_s), p(self.err), st)
+                  p(pl.ext.rowptr), p(pl.ext.src), p(pl.ext.dst), p(pl.ext.rowptr_s), p(pl.ext.perm_s), p(self.err), *ext, st)
         # (msde_plan_build clears *err itself at the start of every build)
         def lists(st_):
             if not self.z_only:       # (the atom-feature lists feed the GIN embedding backward only)

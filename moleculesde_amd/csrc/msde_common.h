@@ -103,12 +103,14 @@ static inline int pick_tpr(int cols) {
 
 // counter-based RNG for dropout masks: the same (seed, index) always gives the same uniform, so
 // backward regenerates the forward mask without storing it.  (splitmix64 finaliser.)
-__device__ __forceinline__ float msde_uniform(unsigned long long seed, unsigned long long idx) {
+__device__ __forceinline__ unsigned long long msde_mix64(unsigned long long seed, unsigned long long idx) {
   unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (idx + 1ull);
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  return (float)(z >> 40) * (1.0f / 16777216.0f);  // 24 random bits -> [0,1)
+  return z ^ (z >> 31);
+}
+__device__ __forceinline__ float msde_uniform(unsigned long long seed, unsigned long long idx) {
+  return (float)(msde_mix64(seed, idx) >> 40) * (1.0f / 16777216.0f);  // 24 random bits -> [0,1)
 }
 
 // N(0,1) from two counter-based uniforms (Box-Muller); the same (seed, index) always gives the same draw

@@ -6,6 +6,7 @@
 // A ∪ A², then (·) ∪ (·)², self loops removed = all ordered pairs within <= 4 bonds -- a per-sample torch_sparse.spspmm
 // on the CPU in the reference), and the host-side plan of round 1 (moleculesde_amd/plan.py: CSR by target + by-source
 // view for bonds and extended edges, pre-offset OGB feature codes, per-table-row atom lists for the embedding backward).
+// msde_plan_build_ext takes the extended rows from the caller instead (sub-graph masking: moleculesde_amd/dataset.py).
 // All outputs are bit-identical to plan.py's (tests/test_gpu_plan.py).
 //
 // Input (device, int32): x_raw [N_cap][K] atom feature codes, bond_src / bond_dst [Eb_cap] (batch-global atom indices,
@@ -122,7 +123,7 @@ plan_molecule_kernel(const int* __restrict__ x_raw, int K, const int* __restrict
                      int* __restrict__ rowptr, int* __restrict__ src, int* __restrict__ dst, int* __restrict__ rowptr_s,
                      int* __restrict__ perm_s, int* __restrict__ bond_codes, float* __restrict__ bond_type,
                      unsigned* __restrict__ ext_rows, int* __restrict__ ext_cnt, int* __restrict__ err, int B, int N_cap,
-                     int Eb_cap) {
+                     int Eb_cap, const unsigned* __restrict__ ext_rows_in) {
   __shared__ short ls[PL_EMAX], ld[PL_EMAX];      // local source / target of the loader-order bonds
   __shared__ short cs[PL_EMAX];                   // local source of the canonical-order bonds
   __shared__ unsigned A[PL_NMAX], P[PL_NMAX];
@@ -190,8 +191,19 @@ plan_molecule_kernel(const int* __restrict__ x_raw, int K, const int* __restrict
     for (int f = 0; f < m; ++f) slot += (cs[f] < s) || (cs[f] == s && f < r);
     perm_s[e0 + slot] = e0 + r;
   }
+  if (ext_rows_in) {
+    // the rows are GIVEN (msde_plan_build_ext: a masked molecule's extended edges are the whole molecule's restricted to the
+    // kept atoms, dataset_3D.py:95-102, not what its kept bonds span).  Sanitised: only bits of this molecule's other atoms
+    if (tid < n) {
+      const unsigned row = ext_rows_in[a0 + tid];
+      const unsigned ok = (n >= 32 ? 0xffffffffu : ((1u << n) - 1u)) & ~(1u << tid);
+      if (row & ~ok) atomicExch(err, 1);
+      A[tid] = row & ok;
+    }
+    __syncthreads();
+  }
   // extend_graph: two rounds of  A <- A | (A·A minus the diagonal)   (dataset_3D.py:12-35)
-  for (int round = 0; round < 2; ++round) {
+  for (int round = 0; round < (ext_rows_in ? 0 : 2); ++round) {
     if (tid < n) {
       unsigned row = A[tid], acc = 0u;
       while (row) { const int k = __ffs(row) - 1; row &= row - 1; acc |= A[k]; }
@@ -377,13 +389,13 @@ plan_lists_fill_kernel(const int* __restrict__ codes, const int* __restrict__ n_
   }
 }
 
-extern "C" int msde_plan_build(const int* x_raw, int K, const int* atom_off, const int* bond_src, const int* bond_dst,
+static int plan_build_impl(const int* x_raw, int K, const int* atom_off, const int* bond_src, const int* bond_dst,
                                const int* bond_attr, const int* bond_off, const int* mol_atoms, const int* mol_bonds,
                                int B, int N_cap, int Eb_cap, int Ee_cap, int P_cap, int Er_cap, int max_nbr, int* mol_ptr,
                                int* bond_ptr, int* pair_ptr, int* sizes, int* batch_i32, int* atom_codes, int* z_codes, int* b_rowptr,
                                int* b_src, int* b_dst, int* b_rowptr_s, int* b_perm_s, int* bond_codes, float* bond_type,
                                unsigned* ext_rows, int* ext_cnt, int* ext_ptr, int* e_rowptr, int* e_src, int* e_dst,
-                               int* e_rowptr_s, int* e_perm_s, int* err, void* stream) {
+                               int* e_rowptr_s, int* e_perm_s, int* err, const unsigned* ext_rows_in, void* stream) {
   if (B <= 0 || B > 1024 || K <= 0 || N_cap <= 0 || P_cap < 0 || Er_cap < 0 || !x_raw || !atom_off || !bond_src || !bond_dst || !bond_attr ||
       !bond_off || !mol_atoms || !mol_bonds || !mol_ptr || !bond_ptr || !pair_ptr || !sizes || !batch_i32 || !atom_codes ||
       !z_codes || !b_rowptr || !b_src || !b_dst || !b_rowptr_s || !b_perm_s || !bond_codes || !bond_type || !ext_rows ||
@@ -395,7 +407,7 @@ extern "C" int msde_plan_build(const int* x_raw, int K, const int* atom_off, con
   MSDE_CHECK_LAUNCH();
   MSDE_LAUNCH(plan_molecule_kernel, dim3(B), dim3(256), 0, st, x_raw, K, atom_off, bond_src, bond_dst, bond_attr, bond_off,
               (const int*)mol_ptr, (const int*)bond_ptr, batch_i32, atom_codes, z_codes, b_rowptr, b_src, b_dst, b_rowptr_s,
-              b_perm_s, bond_codes, bond_type, ext_rows, ext_cnt, err, B, N_cap, Eb_cap);
+              b_perm_s, bond_codes, bond_type, ext_rows, ext_cnt, err, B, N_cap, Eb_cap, ext_rows_in);
   MSDE_CHECK_LAUNCH();
   MSDE_LAUNCH(plan_ext_kernel, dim3(B), dim3(64), 0, st, (const unsigned*)ext_rows, (const int*)mol_ptr,
               (const int*)ext_cnt, B, ext_ptr, sizes + 2, e_rowptr, e_src, e_dst, e_rowptr_s, e_perm_s, N_cap, Ee_cap, err);
@@ -407,6 +419,32 @@ extern "C" int msde_plan_build(const int* x_raw, int K, const int* atom_off, con
               e_rowptr_s, e_perm_s);
   MSDE_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int msde_plan_build(const int* x_raw, int K, const int* atom_off, const int* bond_src, const int* bond_dst,
+                               const int* bond_attr, const int* bond_off, const int* mol_atoms, const int* mol_bonds,
+                               int B, int N_cap, int Eb_cap, int Ee_cap, int P_cap, int Er_cap, int max_nbr, int* mol_ptr,
+                               int* bond_ptr, int* pair_ptr, int* sizes, int* batch_i32, int* atom_codes, int* z_codes, int* b_rowptr,
+                               int* b_src, int* b_dst, int* b_rowptr_s, int* b_perm_s, int* bond_codes, float* bond_type,
+                               unsigned* ext_rows, int* ext_cnt, int* ext_ptr, int* e_rowptr, int* e_src, int* e_dst,
+                               int* e_rowptr_s, int* e_perm_s, int* err, void* stream) {
+  return plan_build_impl(x_raw, K, atom_off, bond_src, bond_dst, bond_attr, bond_off, mol_atoms, mol_bonds, B, N_cap, Eb_cap, Ee_cap, P_cap,
+                         Er_cap, max_nbr, mol_ptr, bond_ptr, pair_ptr, sizes, batch_i32, atom_codes, z_codes, b_rowptr, b_src, b_dst,
+                         b_rowptr_s, b_perm_s, bond_codes, bond_type, ext_rows, ext_cnt, ext_ptr, e_rowptr, e_src, e_dst, e_rowptr_s,
+                         e_perm_s, err, nullptr, stream);
+}
+
+extern "C" int msde_plan_build_ext(const int* x_raw, int K, const int* atom_off, const int* bond_src, const int* bond_dst,
+                               const int* bond_attr, const int* bond_off, const int* mol_atoms, const int* mol_bonds,
+                               int B, int N_cap, int Eb_cap, int Ee_cap, int P_cap, int Er_cap, int max_nbr, int* mol_ptr,
+                               int* bond_ptr, int* pair_ptr, int* sizes, int* batch_i32, int* atom_codes, int* z_codes, int* b_rowptr,
+                               int* b_src, int* b_dst, int* b_rowptr_s, int* b_perm_s, int* bond_codes, float* bond_type,
+                               unsigned* ext_rows, int* ext_cnt, int* ext_ptr, int* e_rowptr, int* e_src, int* e_dst,
+                               int* e_rowptr_s, int* e_perm_s, int* err, const unsigned* ext_rows_in, void* stream) {
+  return plan_build_impl(x_raw, K, atom_off, bond_src, bond_dst, bond_attr, bond_off, mol_atoms, mol_bonds, B, N_cap, Eb_cap, Ee_cap, P_cap,
+                         Er_cap, max_nbr, mol_ptr, bond_ptr, pair_ptr, sizes, batch_i32, atom_codes, z_codes, b_rowptr, b_src, b_dst,
+                         b_rowptr_s, b_perm_s, bond_codes, bond_type, ext_rows, ext_cnt, ext_ptr, e_rowptr, e_src, e_dst, e_rowptr_s,
+                         e_perm_s, err, ext_rows_in, stream);
 }
 
 extern "C" int msde_plan_row_lists(const int* codes, const int* n_dev, int K, int R, int* cnt, int* list_ptr, int* items,

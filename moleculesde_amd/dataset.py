@@ -13,8 +13,11 @@ collated arrays, extend_graph, subtract the centre) and lets DataLoader(shuffle=
   * `DatasetRunner`: the counterpart of pretrain.StreamRunner -- ONE captured graph {gather, plans, forward, backward, Adam};
     an epoch is a loop of replays.  Batches outside the capacities (the short last batch, a molecule of more than 32 atoms)
     take the exact-size eager step on a host-built plan.
-Sub-graph masking (--SSL_masking_ratio; the reference applies it in front of the centring) is not built: its place is a
-per-molecule keep mask read by the gather before the centre is formed.
+Sub-graph masking (--SSL_masking_ratio; Molecule3DDataset.subgraph, dataset_3D.py:53-104, between extend_graph and the
+centring) is a per-molecule keep word: drawn once per epoch for the whole store by msde_dataset_mask_epoch (`bfs_keep` is its
+bit-exact host mirror), read by msde_dataset_gather_batch_masked before the centre is formed, and -- because the masked
+molecule's extended edges are the WHOLE molecule's restricted to the kept atoms, not what the kept bonds span -- handed to
+the device plan builder as ready-made rows (Bucket.ext_in, msde_plan_build_ext).  The captured step itself is the same.
 """
 import numpy as np
 import torch
@@ -27,7 +30,86 @@ FORMAT_VERSION = 1
 _FIELDS = ("x", "positions", "edge_index", "edge_attr", "atom_ptr", "bond_ptr", "ext_count")
 # bits of the gather's error word (csrc/dataset.hip)
 GATHER_ERRORS = {1: "a permutation entry outside [0, M)", 2: "a molecule of more atoms than n_max (or none)",
-                 4: "the batch's atoms or bonds exceed the capacity", 8: "fewer than B molecules remain in the epoch"}
+                 4: "the batch's atoms or bonds exceed the capacity", 8: "fewer than B molecules remain in the epoch",
+                 16: "a keep word that is zero or names atoms the molecule does not have"}
+
+# ---- sub-graph masking: host mirror of csrc/dataset.hip (dataset_mask_epoch_kernel) ---------------------------------------
+_M64 = (1 << 64) - 1
+EPOCH_MIX = 0xD1B54A32D192ED69      # DS_EPOCH_MIX
+
+
+def _mix64(seed, idx):
+    """msde_mix64 (csrc/msde_common.h: the mixer of msde_uniform) on Python integers."""
+    z = (seed + 0x9E3779B97F4A7C15 * (idx + 1)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _keep_count(n, ratio):
+    """Atoms dataset_3D.py:56-62 keeps of n: sub_num = int(n * (1 - ratio)) and `while len(idx_sub) <= sub_num` stops at
+    sub_num + 1 (the script's off-by-one, kept), capped at n."""
+    return min(int(n), int(int(n) * (1 - ratio)) + 1)
+
+
+def keep_counts(ratio, n_max=BK.PLAN_NMAX):
+    """keep_count[n] for n = 0..n_max (int32): the table msde_dataset_mask_epoch reads; Python double arithmetic, on the host."""
+    return np.array([_keep_count(n, ratio) for n in range(int(n_max) + 1)], dtype=np.int32)
+
+
+def _nth_bit(w, j):
+    for _ in range(j):
+        w &= w - 1
+    return (w & -w).bit_length() - 1
+
+
+def bfs_keep(store, ratio, mask_seed, epoch, molecules=None):
+    """The keep words of `molecules` (default: the whole store) for (mask_seed, epoch): Python ints, bit i set = atom i kept.
+    Draw d of molecule m: u = mix64(mix64(mask_seed + EPOCH_MIX * (epoch + 1), m), d) >> 40 (24 bits) picks member
+    (u * count) >> 24, in ascending atom order, of all atoms (d = 0), of the frontier (unkept atoms one stored bond src -> dst
+    from a kept atom) while it is not empty, of all unkept atoms otherwise; keep_count[n] draws.  Integers only: equal to
+    msde_dataset_mask_epoch bit for bit for molecules of <= 32 atoms, and defined the same way for larger ones."""
+    ids = range(len(store)) if molecules is None else [int(i) for i in molecules]
+    seed_e = (int(mask_seed) + EPOCH_MIX * (int(epoch) + 1)) & _M64
+    ei = store.edge_index.numpy()
+    out = []
+    for m in ids:
+        a0, a1, b0, b1 = store._span(m)
+        n = a1 - a0
+        rows = [0] * n
+        for s_, d_ in zip(ei[0, b0:b1].tolist(), ei[1, b0:b1].tolist()):
+            rows[s_] |= 1 << d_
+        key, full, kept, frontier = _mix64(seed_e, m), (1 << n) - 1, 0, 0
+        for d in range(_keep_count(n, ratio)):
+            pool = frontier or (full & ~kept)
+            pick = _nth_bit(pool, ((_mix64(key, d) >> 40) * bin(pool).count("1")) >> 24)
+            kept |= 1 << pick
+            frontier = (frontier | rows[pick]) & ~kept
+        out.append(kept)
+    return out
+
+
+def _kept_atoms(keep, n):
+    """Ascending atom indices of a keep word (int) or a boolean row of length n."""
+    if isinstance(keep, (int, np.integer)):
+        keep = int(keep)
+        if keep <= 0 or keep >> n:
+            raise ValueError(f"keep word {keep:#x} for a molecule of {n} atoms")
+        return [i for i in range(n) if (keep >> i) & 1]
+    row = np.asarray(torch.as_tensor(keep).cpu().numpy(), dtype=bool).reshape(-1)
+    if len(row) != n or not row.any():
+        raise ValueError(f"keep row of {len(row)} entries ({int(row.sum())} set) for a molecule of {n} atoms")
+    return np.nonzero(row)[0].tolist()
+
+
+def ext_rows_of(b):
+    """Per atom of a collated batch the bit mask of its extended neighbours in molecule-local numbering (int32 [N], the
+    contents of Bucket.ext_in), from b.extended_edge_index."""
+    first = torch.cat([torch.zeros(1, dtype=torch.int64), torch.bincount(b.batch, minlength=b.num_graphs).cumsum(0)])[b.batch]
+    src, dst = b.extended_edge_index
+    rows = np.zeros(b.x.size(0), dtype=np.uint32)
+    np.bitwise_or.at(rows, src.numpy(), (np.uint32(1) << (dst - first[src]).numpy().astype(np.uint32)))
+    return torch.from_numpy(rows.view(np.int32))
 
 
 def _ext_counts(edge_index, atom_ptr, bond_ptr):
@@ -178,42 +260,78 @@ class MoleculeStore:
         """dataset_3D.py:120-122 with the arithmetic of csrc/dataset.hip, so that the two agree bit for bit: per axis the
         coordinates are summed in atom order in fp64, divided by n in fp64, rounded to fp32 and subtracted in fp32."""
         a0, a1, _, _ = self._span(i)
-        p = self.positions[a0:a1].numpy()
+        return self._centred(self.positions[a0:a1].numpy())
+
+    @staticmethod
+    def _centred(p):
         s = np.zeros(3, dtype=np.float64)
         for row in p:                           # (sequential on purpose: numpy's own sum is pairwise)
             s = s + row.astype(np.float64)
-        centre = (s / np.float64(a1 - a0)).astype(np.float32)
+        centre = (s / np.float64(len(p))).astype(np.float32)
         return torch.from_numpy(p - centre[None])
 
-    def molecule(self, i, remove_center=False, extended=False):
+    def molecule(self, i, remove_center=False, extended=False, keep=None):
         """Molecule i as a MolData with int64 fields, as the models and Batch.from_data_list expect; `extended` attaches
-        extended_edge_index (dataset_3D.py:116-118), `remove_center` the centred coordinates."""
+        extended_edge_index (dataset_3D.py:116-118), `remove_center` the centred coordinates.  `keep` (a keep word as an int,
+        or a boolean row) is the sub-graph of dataset_3D.py:72-102: kept atoms in ascending order, the bonds with both ends
+        kept in stored order with relabelled ends, extended_edge_index built on the WHOLE molecule and then filtered the same
+        way (two kept atoms joined only through a dropped one stay extended neighbours), the centre over the kept atoms."""
         a0, a1, b0, b1 = self._span(i)
+        n = a1 - a0
         ei = self.edge_index[:, b0:b1].to(torch.int64)
-        d = MolData(x=self.x[a0:a1].to(torch.int64), edge_index=ei, edge_attr=self.edge_attr[b0:b1].to(torch.int64),
-                    positions=self.centred_positions(i) if remove_center else self.positions[a0:a1].clone())
+        if keep is None:
+            d = MolData(x=self.x[a0:a1].to(torch.int64), edge_index=ei, edge_attr=self.edge_attr[b0:b1].to(torch.int64),
+                        positions=self.centred_positions(i) if remove_center else self.positions[a0:a1].clone())
+            if extended:
+                d.extended_edge_index = extend_graph_index(ei, n)
+            return d
+        idx = torch.tensor(_kept_atoms(keep, n), dtype=torch.int64)
+        new = torch.full((n,), -1, dtype=torch.int64)
+        new[idx] = torch.arange(idx.numel())
+
+        def induced(e):                          # (torch_geometric.utils.subgraph with relabel_nodes=True)
+            sel = (new[e[0]] >= 0) & (new[e[1]] >= 0)
+            return new[e[:, sel]], sel
+        ei_k, sel = induced(ei)
+        pos = self.positions[a0:a1][idx]
+        d = MolData(x=self.x[a0:a1][idx].to(torch.int64), edge_index=ei_k, edge_attr=self.edge_attr[b0:b1][sel].to(torch.int64),
+                    positions=self._centred(pos.numpy()) if remove_center else pos.clone())
         if extended:
-            d.extended_edge_index = extend_graph_index(ei, a1 - a0)
+            d.extended_edge_index = induced(extend_graph_index(ei, n))[0]
         return d
 
-    def collate(self, indices, remove_center=True):
-        """The host batch of these molecules, in this order (what the reference's loader would collate)."""
-        return Batch.from_data_list([self.molecule(int(i), remove_center=remove_center, extended=True) for i in indices])
+    def collate(self, indices, remove_center=True, keeps=None):
+        """The host batch of these molecules, in this order (what the reference's loader would collate); `keeps`: one keep
+        word (or boolean row) per molecule."""
+        keeps = [None] * len(indices) if keeps is None else list(keeps)
+        if len(keeps) != len(indices):
+            raise ValueError(f"{len(keeps)} keep words for {len(indices)} molecules")
+        return Batch.from_data_list([self.molecule(int(i), remove_center=remove_center, extended=True, keep=k)
+                                     for i, k in zip(indices, keeps)])
 
-    def epoch_plan(self, epoch, batch_size, shuffle=True, seed=0, rank=0, world=1, perm=None):
-        return EpochPlan(self, epoch, batch_size, shuffle=shuffle, seed=seed, rank=rank, world=world, perm=perm)
+    def epoch_plan(self, epoch, batch_size, shuffle=True, seed=0, rank=0, world=1, perm=None, mask_ratio=0, mask_seed=0):
+        return EpochPlan(self, epoch, batch_size, shuffle=shuffle, seed=seed, rank=rank, world=world, perm=perm,
+                         mask_ratio=mask_ratio, mask_seed=mask_seed)
 
 
 class EpochPlan:
     """One epoch on one rank, host only.  The permutation comes from a CPU torch.Generator seeded by (seed, epoch): the same
     on every rank; the rank's shard is perm[rank::world] cut to the common length.  `needs[key][k]` is what bucket.raw_sizes
     finds on the collated batch k (B, N, E_b, E_e from ext_count, E_r = sum n min(n - 1, 32), P = sum n^2, n_max); the short
-    last batch is kept (drop_last=False, the DataLoader default the reference uses)."""
+    last batch is kept (drop_last=False, the DataLoader default the reference uses).
+    With mask_ratio > 0 the epoch is one of masked molecules (keep words: bfs_keep(store, mask_ratio, mask_seed, epoch)).  The
+    kept atom count depends on n alone, so needs["N"], ["P"] and ["E_r"] are EXACT (from keep_count[n]); needs["E_b"] and
+    ["E_e"] stay the unmasked counts -- UPPER BOUNDS (which bonds survive depends on the draw), so `fits` is a sufficient
+    condition; needs["n_max"] stays the unmasked size: the keep word is 32 bits, a molecule of more than 32 atoms takes the
+    fallback even where its masked size would fit."""
 
-    def __init__(self, store, epoch, batch_size, shuffle=True, seed=0, rank=0, world=1, perm=None):
+    def __init__(self, store, epoch, batch_size, shuffle=True, seed=0, rank=0, world=1, perm=None, mask_ratio=0, mask_seed=0):
         M, B = len(store), int(batch_size)
         if B < 1 or not 0 <= int(rank) < int(world):
             raise ValueError(f"batch_size {B}, rank {rank} of {world}")
+        if not 0 <= float(mask_ratio) < 1:
+            raise ValueError(f"mask_ratio {mask_ratio}: outside [0, 1)")
+        self.store, self.mask_ratio, self.mask_seed = store, float(mask_ratio), int(mask_seed)
         if perm is not None:
             full = np.asarray(torch.as_tensor(perm).cpu().numpy(), dtype=np.int64).reshape(-1)
             if len(full) and (full.min() < 0 or full.max() >= M):
@@ -231,12 +349,13 @@ class EpochPlan:
         if L == 0:
             raise ValueError(f"{len(full)} molecules over {world} ranks leave this rank none")
         self.n_batches, self.n_full = -(-L // B), L // B
-        n = np.diff(store.atom_ptr.numpy())[self.perm]
+        n_all = np.diff(store.atom_ptr.numpy())[self.perm]
+        n = n_all if not self.mask_ratio else keep_counts(self.mask_ratio, int(n_all.max())).astype(np.int64)[n_all]
         per_mol = {"N": n, "E_b": np.diff(store.bond_ptr.numpy())[self.perm], "E_e": store.ext_count.numpy()[self.perm].astype(np.int64),
                    "E_r": n * np.minimum(np.maximum(n - 1, 0), BK.MAX_NBR), "P": n * n}
         starts = np.arange(self.n_batches) * B
         ends = np.minimum(starts + B, L)
-        self.needs = {"B": ends - starts, "n_max": np.maximum.reduceat(n, starts)}
+        self.needs = {"B": ends - starts, "n_max": np.maximum.reduceat(n_all, starts)}
         for k, v in per_mol.items():
             c = np.concatenate([[0], np.cumsum(v, dtype=np.int64)])
             self.needs[k] = c[ends] - c[starts]
@@ -249,6 +368,14 @@ class EpochPlan:
 
     def molecules(self, k):
         return self.perm[k * self.batch_size:(k + 1) * self.batch_size]
+
+    def keeps(self, k):
+        """The keep words of batch k's molecules (host mirror), None without masking."""
+        return bfs_keep(self.store, self.mask_ratio, self.mask_seed, self.epoch, self.molecules(k)) if self.mask_ratio else None
+
+    def collate(self, k, remove_center=True):
+        """The host batch k of this epoch, masked where the plan carries a ratio."""
+        return self.store.collate(self.molecules(k), remove_center=remove_center, keeps=self.keeps(k))
 
     def fits(self, caps):
         """Per batch: does it fit these Caps (bucket.Caps.fits, vectorised)?  The short last batch never does."""
@@ -269,7 +396,8 @@ def caps_for(plan, n_max=None):
 
 class ResidentDataset:
     """The store on the device (uploaded once), the epoch's permutation in a static int32 buffer, the device batch counter
-    and the gather's own error word (Bucket.err is cleared by every msde_plan_build)."""
+    and the gather's own error word (Bucket.err is cleared by every msde_plan_build).  For masked epochs: the whole-molecule
+    extended rows (msde_dataset_ext_rows, once, here) and the keep word of every molecule (msde_dataset_mask_epoch, per epoch)."""
 
     def __init__(self, store, device):
         self.store, self.device = store, torch.device(device)
@@ -283,6 +411,12 @@ class ResidentDataset:
         self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.n_avail = 0
         self._err_host, self._err_event = None, None
+        self.mol_rows = torch.zeros(store.x.size(0), dtype=torch.int32, device=self.device)
+        self.keep = torch.zeros(len(store), dtype=torch.int32, device=self.device)
+        self.keep_count = torch.zeros(BK.PLAN_NMAX + 1, dtype=torch.int32, device=self.device)
+        self.masked = False
+        _lib.call("msde_dataset_ext_rows", _p(self.edge_index), _p(self.atom_ptr), _p(self.bond_ptr), len(store),
+                  self.x.size(0), self.edge_index.size(1), _p(self.mol_rows), _stream())
 
     def epoch_plan(self, epoch, batch_size, **kw):
         return self.store.epoch_plan(epoch, batch_size, **kw)
@@ -295,16 +429,43 @@ class ResidentDataset:
         self.perm[:L].copy_(src.pin_memory() if self.device.type == "cuda" else src, non_blocking=True)
         self.counter.zero_()
         self.n_avail = L
+        self.masked = bool(plan.mask_ratio)
+        if self.masked:
+            self.launch_mask(plan.mask_ratio, plan.mask_seed, plan.epoch)
 
-    def launch_gather(self, blob, layout, caps, n_max=None, remove_center=True, n_avail=None, perm=None, counter=None, err=None):
+    def launch_mask(self, ratio, mask_seed, epoch):
+        """msde_dataset_mask_epoch on the current stream: the keep word of every molecule of the store for (mask_seed, epoch)
+        into self.keep (0 for molecules of more than 32 atoms: the host masks those).  Once per epoch, outside the graph."""
+        src = torch.from_numpy(keep_counts(ratio))
+        self.keep_count.copy_(src.pin_memory() if self.device.type == "cuda" else src, non_blocking=True)
+        _lib.call("msde_dataset_mask_epoch", _p(self.edge_index), _p(self.atom_ptr), _p(self.bond_ptr), len(self.store),
+                  self.x.size(0), self.edge_index.size(1), int(mask_seed) & _M64, int(epoch), _p(self.keep_count),
+                  _p(self.keep), _stream())
+
+    def launch_gather(self, blob, layout, caps, n_max=None, remove_center=True, n_avail=None, perm=None, counter=None, err=None,
+                      ext_in=None, keep=None):
         """msde_dataset_gather_batch on the current stream, unchecked on the host (the kernel's own guards hold): batch
-        `counter[0]` of `perm` into `blob` (int32 [layout['_total']]), then counter[0] += 1."""
+        `counter[0]` of `perm` into `blob` (int32 [layout['_total']]), then counter[0] += 1.  With `ext_in` (int32 [caps.N],
+        Bucket.ext_in): msde_dataset_gather_batch_masked of the molecules masked by `keep` (default: this epoch's words)."""
         lay = layout
         perm = self.perm if perm is None else perm
         assert perm.dtype == torch.int32 and perm.is_contiguous() and blob.dtype == torch.int32 and blob.is_contiguous()
         n_avail = self.n_avail if n_avail is None else int(n_avail)
         if n_avail > perm.numel() or blob.numel() < lay["_total"]:
             raise ValueError(f"n_avail {n_avail} vs a permutation of {perm.numel()}; blob {blob.numel()} vs {lay['_total']} words")
+        if ext_in is not None:
+            keep = self.keep if keep is None else keep
+            assert ext_in.dtype == torch.int32 and ext_in.is_contiguous() and keep.dtype == torch.int32 and keep.is_contiguous()
+            if ext_in.numel() < caps.N or keep.numel() < len(self.store):
+                raise ValueError(f"ext_in {ext_in.numel()} vs {caps.N} atom rows; keep {keep.numel()} vs {len(self.store)} molecules")
+            _lib.call("msde_dataset_gather_batch_masked", _p(self.x), _p(self.pos), _p(self.edge_index), _p(self.edge_attr),
+                      _p(self.atom_ptr), _p(self.bond_ptr), len(self.store), self.x.size(0), self.edge_index.size(1), _p(perm),
+                      _p(self.counter if counter is None else counter), n_avail, caps.B, caps.N, caps.E_b,
+                      int(caps.n_max if n_max is None else n_max), int(bool(remove_center)),
+                      *(lay[k][0] for k in ("x", "pos", "bond_src", "bond_dst", "bond_attr", "mol_atoms", "mol_bonds")),
+                      lay["_total"], _p(keep), _p(self.mol_rows), _p(blob), _p(ext_in), _p(self.err if err is None else err),
+                      _stream())
+            return
         _lib.call("msde_dataset_gather_batch", _p(self.x), _p(self.pos), _p(self.edge_index), _p(self.edge_attr),
                   _p(self.atom_ptr), _p(self.bond_ptr), len(self.store), self.x.size(0), self.edge_index.size(1), _p(perm),
                   _p(self.counter if counter is None else counter), n_avail, caps.B, caps.N, caps.E_b,
@@ -318,8 +479,10 @@ class ResidentDataset:
         if not 0 <= k < plan.n_batches or not bool(plan.fits(bk.caps)[k]):
             raise BK.BucketOverflow(f"batch {k} {plan.need(k) if 0 <= k < plan.n_batches else ''} does not fit the bucket "
                                     f"{bk.caps.as_dict()}")
+        if self.masked and bk.ext_in is None:
+            raise ValueError("a masked epoch needs a bucket with ext_in (Bucket(..., ext_in=True))")
         self.counter.fill_(k)
-        self.launch_gather(bk.raw, bk.layout, bk.caps, remove_center=remove_center)
+        self.launch_gather(bk.raw, bk.layout, bk.caps, remove_center=remove_center, ext_in=bk.ext_in if self.masked else None)
 
     def poll_error(self):
         """The gather's error word WITHOUT a synchronisation (Bucket.poll_overflow's scheme): the word as it was when the
@@ -343,7 +506,10 @@ def describe_error(bits):
 class DatasetRunner:
     """pretrain.StreamRunner's surface (ensure_captured / run / fallbacks) on a resident dataset: ONE bucket, ONE captured graph
     {gather of batch `counter` + device-side plans + forward + backward + Adam}; a step is one replay, nothing is copied
-    from or packed on the host.  run(plan, steps) takes an EpochPlan where StreamRunner.run takes batches."""
+    from or packed on the host.  run(plan, steps) takes an EpochPlan where StreamRunner.run takes batches.
+    A plan with a mask ratio makes it the masked runner: the graph holds the masked gather and the plan build on Bucket.ext_in,
+    every epoch's plan must carry a ratio too (the keep words are redrawn per epoch, outside the graph), and the fallbacks
+    collate host-masked molecules of the same (mask_seed, epoch)."""
 
     def __init__(self, trainer, resident, plan, caps=None, remove_center=True):
         from . import pretrain as PT
@@ -354,7 +520,10 @@ class DatasetRunner:
         if not bool(fits[0]):
             raise BK.BucketOverflow(f"the first batch {plan.need(0)} does not fit the bucket {self.caps.as_dict()}")
         self._check_neg_samples(plan)
+        self.masked = bool(plan.mask_ratio)
         self.bk = bk = trainer.make_bucket(self.caps)
+        if self.masked:
+            bk.alloc_ext_in()
         self.fallbacks = 0
         # warm up as Trainer.capture_bucket does: batch 0 gathered eagerly, its plans, two eager steps; then capture
         resident.begin_epoch(plan)
@@ -370,7 +539,8 @@ class DatasetRunner:
         self._capture()
 
     def _gather(self):
-        self.rd.launch_gather(self.bk.raw, self.bk.layout, self.caps, remove_center=self.remove_center, n_avail=self.n_avail)
+        self.rd.launch_gather(self.bk.raw, self.bk.layout, self.caps, remove_center=self.remove_center, n_avail=self.n_avail,
+                              ext_in=self.bk.ext_in if self.masked else None)
 
     def _capture(self):
         tr, PT = self.tr, self.PT
@@ -399,6 +569,8 @@ class DatasetRunner:
             return 0
         if len(plan.perm) != self.n_avail:
             raise ValueError(f"an epoch of {len(plan.perm)} molecules on a graph captured for {self.n_avail}")
+        if bool(plan.mask_ratio) != self.masked:
+            raise ValueError(f"an epoch with mask_ratio {plan.mask_ratio} on a graph captured {'with' if self.masked else 'without'} masking")
         fits = plan.fits(self.caps)
         self._check_neg_samples(plan)
         rd, bk, tr = self.rd, self.bk, self.tr
@@ -412,18 +584,30 @@ class DatasetRunner:
                 tr.step_graph(bk.batch)
             else:                               # exact-size eager step on a host-built plan; the device counter moves on
                 self.fallbacks += 1
-                b = rd.store.collate(plan.molecules(k), remove_center=self.remove_center)
-                tr.step(self.PT.prepare_batch(b, tr.device))
+                tr.step(self.PT.prepare_batch(plan.collate(k, remove_center=self.remove_center), tr.device))
                 rd.counter.add_(1)
         return n
 
 
 class EagerDatasetRunner:
-    """The exact-size loop over host-collated batches of the same epoch plans (pretrain --eager --dataset_file)."""
+    """The exact-size loop over host-collated batches of the same epoch plans (pretrain --eager --dataset_file).
+    `start_plan`: take DatasetRunner's start on that plan -- its two warm-up updates on the plan's first batch, then every
+    draw seeded by the device step counter as Trainer.capture arranges for a captured step -- so that this loop is the eager
+    twin of the replayed run: same updates, same draws, same epoch losses.  pretrain.main asks for it under
+    --SSL_masking_ratio, where the two modes of one command are meant to agree; without it the loop starts as it always did."""
     fallbacks = 0
 
-    def __init__(self, trainer, store, remove_center=True):
+    def __init__(self, trainer, store, remove_center=True, start_plan=None):
         self.tr, self.store, self.remove_center = trainer, store, bool(remove_center)
+        if start_plan is not None:
+            from .geom3d import prepare_batch
+            b = prepare_batch(start_plan.collate(0, remove_center=self.remove_center), trainer.device)
+            for _ in range(2):
+                trainer.step(b)
+            sd = trainer.step_counter.view(torch.int64)
+            trainer.models["SDE_2Dto3D_model"].score_network.seed_dev = sd
+            if hasattr(trainer.noise, "seed_dev"):
+                trainer.noise.seed_dev = sd
 
     def ensure_captured(self):
         pass
@@ -432,5 +616,5 @@ class EagerDatasetRunner:
         from .geom3d import prepare_batch
         n = plan.n_batches if steps is None else min(int(steps), plan.n_batches)
         for k in range(n):
-            self.tr.step(prepare_batch(self.store.collate(plan.molecules(k), remove_center=self.remove_center), self.tr.device))
+            self.tr.step(prepare_batch(plan.collate(k, remove_center=self.remove_center), self.tr.device))
         return n

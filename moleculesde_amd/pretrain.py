@@ -1062,19 +1062,39 @@ def main_parser():
     p.add_argument("--no_shuffle", action="store_true", help="epochs in the store's order (--dataset_file)")
     p.add_argument("--keep_center", action="store_true",
                    help="do not subtract each molecule's centre (the reference script passes remove_center=True)")
+    p.add_argument("--SSL_masking_ratio", type=float, default=0.0,
+                   help="train on a random BFS sub-graph of every molecule, redrawn per epoch, that drops about this share of "
+                        "its atoms (Molecule3DDataset.subgraph; needs --dataset_file).  Default 0: whole molecules, as before "
+                        "this flag existed; the reference's default (examples/config.py) is --SSL_masking_ratio 0.15")
+    p.add_argument("--mask_seed", type=int, default=0, help="seed of the sub-graph draws (--SSL_masking_ratio)")
     return p
+
+
+def parse_main_args(argv=None):
+    """main_parser().parse_args with the checks that span flags."""
+    p = main_parser()
+    args = p.parse_args(argv)
+    if not 0 <= args.SSL_masking_ratio < 1:
+        p.error(f"--SSL_masking_ratio {args.SSL_masking_ratio}: outside [0, 1)")
+    if args.SSL_masking_ratio > 0 and not args.dataset_file:
+        p.error("--SSL_masking_ratio masks the molecules of a store: it needs --dataset_file (the synthetic batches are pre-packed)")
+    return args
 
 
 def _main_dataset(args, trainer, rank, world):
     """main() on a molecule store (--dataset_file): the store is uploaded once and every epoch is a loop of graph replays
     fed by csrc/dataset.hip (dataset.DatasetRunner); under --eager the exact-size loop over host-collated batches of the same
-    epoch plans.  Capacities: dataset.caps_for on epoch 1.  Under data parallelism each rank takes its shard."""
+    epoch plans.  Capacities: dataset.caps_for on epoch 1.  Under data parallelism each rank takes its shard.  With
+    --SSL_masking_ratio every epoch plan carries the ratio and --mask_seed: both runners then train on masked molecules."""
     from . import dataset as DS
     store = DS.MoleculeStore.load(args.dataset_file)
-    kw = dict(shuffle=not args.no_shuffle, seed=args.shuffle_seed, rank=rank, world=world)
+    kw = dict(shuffle=not args.no_shuffle, seed=args.shuffle_seed, rank=rank, world=world,
+              mask_ratio=args.SSL_masking_ratio, mask_seed=args.mask_seed)
     plan_of = lambda epoch: store.epoch_plan(epoch, args.batch_size, **kw)
     if args.eager:
-        runner = DS.EagerDatasetRunner(trainer, store, remove_center=not args.keep_center)
+        # (masked: the eager twin of the replayed run, DatasetRunner's start included; unmasked: the loop as it always was)
+        runner = DS.EagerDatasetRunner(trainer, store, remove_center=not args.keep_center,
+                                       start_plan=plan_of(1) if args.SSL_masking_ratio > 0 else None)
     else:
         runner = DS.DatasetRunner(trainer, DS.ResidentDataset(store, trainer.device), plan_of(1),
                                   remove_center=not args.keep_center)
@@ -1089,7 +1109,7 @@ def main(argv=None):
     launches on exact-size batches (the round-1 loop); InfoNCE_dot_prod and EBM_dot_prod take that loop too unless
     `--captured_cl` is given."""
     from .synthetic import make_batch
-    args = main_parser().parse_args(argv)
+    args = parse_main_args(argv)
     if not args.eager and args.SDE_coeff_contrastive > 0 and args.CL_similarity_metric not in bucket_cl_metrics(args):
         print(f"CL_similarity_metric={args.CL_similarity_metric}: the captured bucket step takes EBM_node_dot_prod only, "
               "training on resident exact-size batches (--eager); --captured_cl runs this metric in the captured step",
