@@ -453,25 +453,21 @@ class ResidentDataset:
         n_avail = self.n_avail if n_avail is None else int(n_avail)
         if n_avail > perm.numel() or blob.numel() < lay["_total"]:
             raise ValueError(f"n_avail {n_avail} vs a permutation of {perm.numel()}; blob {blob.numel()} vs {lay['_total']} words")
-        if ext_in is not None:
-            keep = self.keep if keep is None else keep
-            assert ext_in.dtype == torch.int32 and ext_in.is_contiguous() and keep.dtype == torch.int32 and keep.is_contiguous()
-            if ext_in.numel() < caps.N or keep.numel() < len(self.store):
-                raise ValueError(f"ext_in {ext_in.numel()} vs {caps.N} atom rows; keep {keep.numel()} vs {len(self.store)} molecules")
-            _lib.call("msde_dataset_gather_batch_masked", _p(self.x), _p(self.pos), _p(self.edge_index), _p(self.edge_attr),
-                      _p(self.atom_ptr), _p(self.bond_ptr), len(self.store), self.x.size(0), self.edge_index.size(1), _p(perm),
-                      _p(self.counter if counter is None else counter), n_avail, caps.B, caps.N, caps.E_b,
-                      int(caps.n_max if n_max is None else n_max), int(bool(remove_center)),
-                      *(lay[k][0] for k in ("x", "pos", "bond_src", "bond_dst", "bond_attr", "mol_atoms", "mol_bonds")),
-                      lay["_total"], _p(keep), _p(self.mol_rows), _p(blob), _p(ext_in), _p(self.err if err is None else err),
-                      _stream())
-            return
-        _lib.call("msde_dataset_gather_batch", _p(self.x), _p(self.pos), _p(self.edge_index), _p(self.edge_attr),
-                  _p(self.atom_ptr), _p(self.bond_ptr), len(self.store), self.x.size(0), self.edge_index.size(1), _p(perm),
+        common = (_p(self.x), _p(self.pos), _p(self.edge_index), _p(self.edge_attr), _p(self.atom_ptr), _p(self.bond_ptr),
+                  len(self.store), self.x.size(0), self.edge_index.size(1), _p(perm),
                   _p(self.counter if counter is None else counter), n_avail, caps.B, caps.N, caps.E_b,
                   int(caps.n_max if n_max is None else n_max), int(bool(remove_center)),
                   *(lay[k][0] for k in ("x", "pos", "bond_src", "bond_dst", "bond_attr", "mol_atoms", "mol_bonds")),
-                  lay["_total"], _p(blob), _p(self.err if err is None else err), _stream())
+                  lay["_total"])
+        tail = (_p(self.err if err is None else err), _stream())
+        if ext_in is None:
+            _lib.call("msde_dataset_gather_batch", *common, _p(blob), *tail)
+            return
+        keep = self.keep if keep is None else keep
+        assert ext_in.dtype == torch.int32 and ext_in.is_contiguous() and keep.dtype == torch.int32 and keep.is_contiguous()
+        if ext_in.numel() < caps.N or keep.numel() < len(self.store):
+            raise ValueError(f"ext_in {ext_in.numel()} vs {caps.N} atom rows; keep {keep.numel()} vs {len(self.store)} molecules")
+        _lib.call("msde_dataset_gather_batch_masked", *common, _p(keep), _p(self.mol_rows), _p(blob), _p(ext_in), *tail)
 
     def gather(self, bk, plan, k, remove_center=True):
         """Host-checked gather of batch k of `plan` (after begin_epoch(plan)) into a bucket: refuses, before any launch, a

@@ -90,6 +90,30 @@ def test_extended_edges_of_a_masked_molecule_are_induced_not_recomputed(store):
             store.molecule(PATH6, keep=bad)
 
 
+@pytest.mark.parametrize("remove_center", [True, False], ids=["centred", "raw"])
+def test_full_keep_words_collate_the_whole_molecules(store, remove_center):
+    """The CPU twin of tests/test_gpu_dataset_mask.py::test_full_keep_words_make_the_masked_gather_the_unmasked_one."""
+    from moleculesde_amd.dataset import ext_rows_of
+    n = np.diff(store.atom_ptr.numpy())
+    plan = store.epoch_plan(1, B, seed=3)
+    for k in range(plan.n_batches):
+        mols = plan.molecules(k)
+        whole = store.collate(mols, remove_center=remove_center)
+        full = store.collate(mols, remove_center=remove_center, keeps=[(1 << int(n[int(m)])) - 1 for m in mols])
+        assert sorted(full.tensor_keys()) == sorted(whole.tensor_keys()) and full.num_graphs == whole.num_graphs
+        for key in whole.tensor_keys():
+            a, b = getattr(full, key), getattr(whole, key)
+            assert a.dtype == b.dtype and torch.equal(a, b), (k, key)
+        rows = []                                                     # extend_graph_index of each whole molecule, as words
+        for m in mols:
+            d = store.molecule(int(m))
+            r = [0] * d.x.size(0)
+            for s, t in extend_graph_index(d.edge_index, d.x.size(0)).t().tolist():
+                r[s] |= 1 << t
+            rows += r
+        assert [int(w) & 0xFFFFFFFF for w in ext_rows_of(full).tolist()] == rows
+
+
 def test_masked_epoch_plan_needs_are_exact_for_atoms_and_bounds_for_edges(store):
     for r in (0.15, 0.5):
         plan = store.epoch_plan(2, B, seed=4, mask_ratio=r, mask_seed=9)

@@ -7,6 +7,8 @@ msde_plan_build_ext, moleculesde_amd/dataset.py).
 4. msde_plan_build_ext on that bucket == the host plan of the host-masked batch; for the path of 6 atoms with atom 1 dropped
    it differs from what msde_plan_build derives from the same blob (the induced extended edges).
 5. Guards.  6. DatasetRunner replays == the eager twin.  7. The short last batch.  8. pretrain.main (two tests).
+9. The masked and the unmasked gather are two forms of one kernel: with full keep words the blobs are equal bit for bit, and
+   the guards they share raise the same bits through either entry point.
 """
 import math
 import types
@@ -162,6 +164,38 @@ def test_masked_gather_blob_equals_pack_raw_of_the_host_masked_batch(dev, case, 
         _check_blob(case, bk, whole.molecules(k), [keeps[int(m)] for m in whole.molecules(k)], remove_center)
 
 
+def _full_keeps(case, dev):
+    return _keep_tensor([(1 << int(n)) - 1 for n in case.n], dev)
+
+
+@pytest.mark.parametrize("remove_center", [True, False], ids=["centred", "raw"])
+def test_full_keep_words_make_the_masked_gather_the_unmasked_one(dev, case, remove_center):
+    """The two forms of dataset_gather_kernel are one algorithm: with every atom kept the masked form writes the unmasked
+    form's blob bit for bit, and ext_in is the whole molecules' rows (the compress step is the identity).  Every batch."""
+    rd, whole, caps = case.rd, case.whole, case.caps
+    rd.begin_epoch(whole)
+    a, b = case.BK.Bucket(caps, dev), case.BK.Bucket(caps, dev, ext_in=True)
+    full = _full_keeps(case, dev)
+    ptr = case.store.atom_ptr.numpy()
+    rows = rd.mol_rows.cpu()
+    ctr_a, ctr_b = (torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(2))
+    err_a, err_b = (torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(2))
+    for k in range(whole.n_batches):
+        for t in (a.raw, b.raw, b.ext_in):
+            t.fill_(-1)
+        rd.launch_gather(a.raw, a.layout, caps, remove_center=remove_center, counter=ctr_a, err=err_a)
+        rd.launch_gather(b.raw, b.layout, caps, remove_center=remove_center, counter=ctr_b, err=err_b, ext_in=b.ext_in, keep=full)
+        torch.cuda.synchronize()
+        assert int(err_a.cpu()) == 0 and int(err_b.cpu()) == 0 and int(ctr_a.cpu()) == k + 1 == int(ctr_b.cpu())
+        diff = (a.raw != b.raw).nonzero().flatten()
+        assert diff.numel() == 0, (k, diff[:8].tolist(), dict(a.layout))
+        assert bool((a.raw != -1).any())
+        atoms = torch.from_numpy(np.concatenate([np.arange(ptr[int(m)], ptr[int(m) + 1]) for m in whole.molecules(k)]))
+        N = atoms.numel()
+        assert N == whole.need(k)["N"] and torch.equal(b.ext_in[:N].cpu(), rows[atoms]), k
+        assert not bool(b.ext_in[N:].any())
+
+
 def test_plan_build_ext_equals_the_host_plan_and_differs_from_the_bond_derived_one(dev, case):
     from test_gpu_plan import _check_plan_equal
     rd, whole = case.rd, case.whole
@@ -239,6 +273,49 @@ def test_guards_bad_keep_words_write_nothing_and_bad_rows_are_sanitised(dev, cas
     bk.build_plan_on_device()
     torch.cuda.synchronize()
     assert int(bk.err.cpu()) == 0
+
+
+def test_shared_guards_report_the_same_bits_through_both_entry_points(dev, case):
+    """The four argument guards of tests/test_gpu_dataset.py::test_guards_write_nothing_and_set_the_error_word on this store,
+    through the masked entry with full keep words: the error word is exactly the bit the unmasked entry raises for the same
+    input, blob, ext_in and their guard bands keep the valid previous gather, the counter advances."""
+    rd, whole, BK, M = case.rd, case.whole, case.BK, len(case.store)
+    rd.begin_epoch(whole)
+    atoms = [whole.need(k)["N"] for k in range(5)]
+    k_big, k_prev = int(np.argmax(atoms)), int(np.argmin(atoms))
+    k32 = next(k for k in range(5) if whole.need(k)["n_max"] == 32)
+    assert atoms[k_prev] < atoms[k_big]                              # the previous batch fits the capacity one row short
+    tight = types.SimpleNamespace(B=B, N=atoms[k_big] - 1, E_b=case.caps.E_b, n_max=32)
+    bad_perm = torch.from_numpy(whole.perm.astype(np.int32)).to(dev)
+    bad_perm[3] = M
+    full = _full_keeps(case, dev)
+    GUARD, SENT = 64, -0x5A5A5A5B
+    cases = [("perm entry == M", case.caps, dict(perm=bad_perm), 0, 1),
+             ("32 atoms, n_max 24", case.caps, dict(n_max=24), k32, 2),
+             ("capacity one row short", tight, dict(), k_big, 4),
+             ("fewer than B remain", case.caps, dict(n_avail=B * 5 - 1), 4, 8)]
+    for what, caps, kw, k, bit in cases:
+        lay = BK.raw_layout(caps)
+        buf = torch.full((GUARD + lay["_total"] + GUARD,), SENT, dtype=torch.int32, device=dev)
+        ebuf = torch.full((GUARD + caps.N + GUARD,), SENT, dtype=torch.int32, device=dev)
+        ubuf = buf.clone()                                           # the unmasked entry's blob
+        blob, ext_in, ublob = buf[GUARD:GUARD + lay["_total"]], ebuf[GUARD:GUARD + caps.N], ubuf[GUARD:GUARD + lay["_total"]]
+        ctr = torch.full((1,), k_prev, dtype=torch.int32, device=dev)
+        err, uerr = (torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(2))
+        rd.launch_gather(blob, lay, caps, counter=ctr, err=err, ext_in=ext_in, keep=full)         # a valid previous batch
+        before, ebefore = buf.clone(), ebuf.clone()
+        assert int(err.cpu()) == 0 and bool((blob != SENT).any()) and bool((ext_in != SENT).all())
+        uctr = torch.full((1,), k, dtype=torch.int32, device=dev)
+        rd.launch_gather(ublob, lay, caps, counter=uctr, err=uerr, **kw)
+        ctr.fill_(k)
+        rd.launch_gather(blob, lay, caps, counter=ctr, err=err, ext_in=ext_in, keep=full, **kw)
+        torch.cuda.synchronize()
+        assert int(uerr.cpu()) == bit and int(err.cpu()) == bit, (what, int(uerr.cpu()), int(err.cpu()))
+        assert torch.equal(buf, before) and torch.equal(ebuf, ebefore), what + ": blob, ext_in and guard bands untouched"
+        for t in (buf, ebuf):
+            assert bool((t[:GUARD] == SENT).all()) and bool((t[-GUARD:] == SENT).all()), what
+        assert bool((ubuf == SENT).all()), what
+        assert int(ctr.cpu()) == k + 1 == int(uctr.cpu())
 
 
 def _trainer(args, dev, seed):
