@@ -351,7 +351,8 @@ int msde_edge_attention_fwd(const float* q, const float* k, const float* v,
                             const unsigned long long* seed_dev, float* alpha, float* out,
                             void* stream);
 /* backward of the above: writes g_q [N,D], g_ee [E,D] (row stride ld_ee, like ee) and the per-edge grads
- * g_kpe/g_vpe [E,D] (to be segment-summed by source into g_k / g_v with msde_segment_sum_rows). */
+ * g_kpe/g_vpe [E,D] (to be segment-summed by source into g_k / g_v with msde_segment_sum_rows).
+ * MSDE_EINVAL if any row stride (ld, ldg, ld_ee, ld_kv) is below D, as in the forward. */
 int msde_edge_attention_bwd(const float* g_out, const float* q, const float* k, const float* v,
                             int ld, float* g_skip /* may be NULL, else receives g_out */,
                             int ldg /* row stride of g_q and g_skip */,

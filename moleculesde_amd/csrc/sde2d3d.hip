@@ -445,7 +445,8 @@ extern "C" int msde_edge_attention_bwd(const float* g_out, const float* q, const
     return MSDE_EINVAL;
   if (ld_ee == 0) ld_ee = H * Ch;
   if (ld_kv == 0) ld_kv = H * Ch;
-  if (p_drop < 0.f || p_drop >= 1.f || ld_ee < H * Ch || ld_kv < H * Ch) return MSDE_EINVAL;
+  if (p_drop < 0.f || p_drop >= 1.f || ld < H * Ch || ld_ee < H * Ch || ld_kv < H * Ch) return MSDE_EINVAL;
+  if (ldg < H * Ch) return MSDE_EINVAL;      // row stride of g_q (always written) and of g_skip
   if (N == 0) return 0;
   if (ea_wave_path() && H == 8 && Ch == 4 && ld % 4 == 0 && ld_ee % 4 == 0 && ld_kv % 4 == 0 && ldg % 4 == 0 &&
       ea_al16(g_out) && ea_al16(q) && ea_al16(k) && ea_al16(v) && ea_al16(ee) && ea_al16(g_q) && ea_al16(g_ee) &&

@@ -1057,7 +1057,7 @@ class _EdgeAttentionFused(torch.autograd.Function):
                 ctx.shared["left"] = ld_ee // D
             ctx.shared["left"] -= 1
             if ctx.shared["left"] == 0:
-                del ctx.shared["g_ee"]          # the buffer now lives in the autograd graph only
+                ctx.shared.clear()              # the buffer now lives in the autograd graph only
         g_kv = torch.empty(E, 2 * D, dtype=torch.float32, device=g.device)     # [g_kpe | g_vpe] per edge
         base, gbase = qkvs.data_ptr(), g_qkvs.data_ptr()
         pq, pk, pv = (ctypes.c_void_p(base + 4 * D * j) for j in range(3))

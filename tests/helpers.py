@@ -195,6 +195,14 @@ ESCORE_SPECS = [(20, "hub"), (21, "hub"), (32, "hub"), (32, "chain"), (17, "rand
 ESCORE_EM = [380, 420, 992, 236, None, None, None, 552, 132]     # None: whatever the random tree gives (checked < 384)
 
 
+# batch of the score-graph kernel tests (tests/test_gpu_score_graph.py), built with seed SCORE_GRAPH_SEED; its node / edge
+# counts and in-degrees ({0, 1, 2, 7..16, 63, 64, 65, 99}, first and last node without in-edges, N odd and 3 mod 4) are
+# pinned on the host by tests/test_score_graph_host.py
+SCORE_GRAPH_SPECS = [(1, "chain"), (2, "chain"), (8, "hub"), (9, "hub"), (10, "hub"), (64, "hub"), (65, "hub"), (66, "hub"),
+                     (100, "hub"), (17, "random"), (3, "chain"), (1, "chain"), (1, "chain")]
+SCORE_GRAPH_SEED = 3
+
+
 def loss_specs(n_max):
     """Ragged 3D->2D batch: n_max- (or 32-), 21-, 17-, 2- and 1-atom molecules, a dense n_max-atom molecule and a hub whose atom
     n_max - 3 (row >= 20) is bondless."""
