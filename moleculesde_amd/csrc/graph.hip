@@ -111,6 +111,8 @@ extern "C" int msde_radius_fill(const float* pos, const int* batch, const int* m
                                 int max_nbr, const int* rowptr, int* src, int* dst, float* dist, int E_cap,
                                 void* stream) {
   if (N < 0 || E_cap < 0 || !rowptr) return MSDE_EINVAL;
+  if (N > 0 && (!pos || !batch || !mol_ptr)) return MSDE_EINVAL;
+  if (E_cap > 0 && (!src || !dst || !dist)) return MSDE_EINVAL;
   if (N == 0 && E_cap == 0) return 0;
   int work = N > 0 ? N : 1;
   MSDE_LAUNCH(radius_fill_kernel, dim3((work + 255) / 256), dim3(256), 0, as_stream(stream), pos, batch,

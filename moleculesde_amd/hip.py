@@ -285,9 +285,18 @@ def pair_capacity(pl):
     return int(p2) if p2 is not None else (int(pl.E_r_cap) + 1) // 2
 
 
+PAIR_NMAX = 33         # atoms per molecule up to which the 32-neighbour cap cannot bind: the pair form's premise
+
+
 def pair_plan(pos, pl, cutoff):
     """Pair list + distances of the batch on the device, one launch, no host synchronisation (replaces the radius graph of
-    schnet.py:91-93 for molecules the 32-neighbour cap cannot bind on)."""
+    schnet.py:91-93 for molecules the 32-neighbour cap cannot bind on).  A plan that knows its largest molecule (N_max of
+    plan.build_plan, the size bound of a capacity bucket) and has it above PAIR_NMAX is refused here: the pair kernels trust
+    their caller on it."""
+    n_max = getattr(pl, "N_max", None)
+    if n_max is not None and int(n_max) > PAIR_NMAX:
+        raise ValueError(f"pair_plan: molecules of up to {int(n_max)} atoms; the pair form holds at most {PAIR_NMAX} "
+                         "(above that the radius graph's 32-neighbour cap binds: use the per-edge kernels)")
     pos = _f32(pos.detach())
     dev = pos.device
     pp = PairPlan()

@@ -203,6 +203,15 @@ SCORE_GRAPH_SPECS = [(1, "chain"), (2, "chain"), (8, "hub"), (9, "hub"), (10, "h
 SCORE_GRAPH_SEED = 3
 
 
+# batches of the CFConv size tests (tests/test_gpu_cfconv_sizes.py; graphs, references and tolerances in tests/cfconv_cases.py);
+# tests/test_cfconv_sizes_host.py pins their node / edge counts, in- and out-degrees and chunk offsets on the host
+CFCONV_PAIR_SPECS = [(1, "chain"), (33, "hub"), (2, "chain"), (33, "random"), (21, "random"), (3, "chain"), (31, "dense"),
+                     (32, "random"), (20, "hub"), (1, "chain")]
+CFCONV_PAIR_SEED = 5               # N_max = 33: the pair form applies; radius graph symmetric, in-degrees up to 32
+CFCONV_CAP_SPECS = [(34, "hub"), (40, "random"), (65, "chain"), (1, "chain"), (33, "hub"), (7, "random")]
+CFCONV_CAP_SEED = 6                # N_max = 65: the 32-neighbour cap binds; asymmetric graph, by-source rows up to 64
+
+
 def loss_specs(n_max):
     """Ragged 3D->2D batch: n_max- (or 32-), 21-, 17-, 2- and 1-atom molecules, a dense n_max-atom molecule and a hub whose atom
     n_max - 3 (row >= 20) is bondless."""
