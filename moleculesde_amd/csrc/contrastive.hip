@@ -14,7 +14,8 @@ __device__ __forceinline__ float bce_logits(float x, float z) {
 }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
-template <int V>
+// P: column passes as a compile-time constant (LAUNCH_ROWS_PASSES in msde_common.h; 0 = the run-time column loop)
+template <int V, int P>
 __global__ void cl_rows_kernel(const float* __restrict__ X, const float* __restrict__ Y, const int* __restrict__ perm1,
                                const int* __restrict__ perm2, int N, const int* __restrict__ Ndev, int cols, int tpr,
                                float invT, float* __restrict__ rows, int* __restrict__ inv1, int* __restrict__ inv2) {
@@ -34,11 +35,28 @@ __global__ void cl_rows_kernel(const float* __restrict__ X, const float* __restr
   const T* y1 = reinterpret_cast<const T*>(Y) + (size_t)j1 * cols;
   const T* x2 = reinterpret_cast<const T*>(X) + (size_t)j2 * cols;
   float p = 0.f, n1 = 0.f, n2 = 0.f;
-  for (int c = lane; c < cols; c += tpr) {
-    T xv = x[c], yv = y[c];
-    p += vhsum(vmul(xv, yv));
-    n1 += vhsum(vmul(xv, y1[c]));
-    n2 += vhsum(vmul(yv, x2[c]));
+  if constexpr (P > 0) {              // all passes' rows requested at once; same lane -> column mapping, same pass order
+    T xv[P], yv[P], y1v[P], x2v[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+      const int c = min(lane + q * tpr, cols - 1);
+      xv[q] = x[c]; yv[q] = y[c]; y1v[q] = y1[c]; x2v[q] = x2[c];
+    }
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+      if (lane + q * tpr < cols) {
+        p += vhsum(vmul(xv[q], yv[q]));
+        n1 += vhsum(vmul(xv[q], y1v[q]));
+        n2 += vhsum(vmul(yv[q], x2v[q]));
+      }
+    }
+  } else {
+    for (int c = lane; c < cols; c += tpr) {
+      T xv = x[c], yv = y[c];
+      p += vhsum(vmul(xv, yv));
+      n1 += vhsum(vmul(xv, y1[c]));
+      n2 += vhsum(vmul(yv, x2[c]));
+    }
   }
   p = group_sum(p, tpr); n1 = group_sum(n1, tpr); n2 = group_sum(n2, tpr);
   if (lane == 0) {
@@ -71,7 +89,7 @@ __global__ void __launch_bounds__(1024) cl_reduce_kernel(const float* __restrict
   }
 }
 
-template <int V>
+template <int V, int P>
 __global__ void cl_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Y, const int* __restrict__ perm1,
                               const int* __restrict__ perm2, const int* __restrict__ inv1, const int* __restrict__ inv2,
                               const float* __restrict__ rows, const float* __restrict__ g_loss, int N,
@@ -103,6 +121,31 @@ __global__ void cl_bwd_kernel(const float* __restrict__ X, const float* __restri
   const T* Yv = reinterpret_cast<const T*>(Y);
   T* gXv = reinterpret_cast<T*>(gX) + (size_t)i * cols;
   T* gYv = reinterpret_cast<T*>(gY) + (size_t)i * cols;
+  if constexpr (P > 0) {              // the six rows of all passes requested at once, then combined and stored pass by pass
+    T xi[P], yi[P], yj1[P], yk2[P], xj2[P], xk1[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+      const int c = min(lane + q * tpr, cols - 1);
+      xi[q] = Xv[(size_t)i * cols + c]; yi[q] = Yv[(size_t)i * cols + c];
+      yj1[q] = Yv[(size_t)j1 * cols + c]; yk2[q] = Yv[(size_t)k2 * cols + c];
+      xj2[q] = Xv[(size_t)j2 * cols + c]; xk1[q] = Xv[(size_t)k1 * cols + c];
+    }
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+      const int c = lane + q * tpr;
+      if (c < cols) {
+        T gx = vscale(yi[q], dp);
+        gx = vadd(gx, vscale(yj1[q], dn1));
+        gx = vadd(gx, vscale(yk2[q], dn2k));
+        T gy = vscale(xi[q], dp);
+        gy = vadd(gy, vscale(xj2[q], dn2));
+        gy = vadd(gy, vscale(xk1[q], dn1k));
+        gXv[c] = gx;
+        gYv[c] = gy;
+      }
+    }
+    return;
+  }
   for (int c = lane; c < cols; c += tpr) {
     T xi = Xv[(size_t)i * cols + c], yi = Yv[(size_t)i * cols + c];
     T gx = vscale(yi, dp);
@@ -121,7 +164,7 @@ extern "C" int msde_cl_ebm_fwd(const float* X, const float* Y, const int* perm1,
                                void* stream) {
   if (N <= 0 || D <= 0 || !X || !Y || !perm1 || !perm2 || !rows || !inv1 || !inv2 || !out) return MSDE_EINVAL;
   const int* ndev = rows_dev;
-  LAUNCH_ROWS(cl_rows_kernel, N, D, X, Y, perm1, perm2, N, ndev, cols, tpr, invT, rows, inv1, inv2);
+  LAUNCH_ROWS_PASSES(cl_rows_kernel, N, D, X, Y, perm1, perm2, N, ndev, cols, tpr, invT, rows, inv1, inv2);
   MSDE_CHECK_LAUNCH();
   MSDE_LAUNCH(cl_reduce_kernel, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)rows, N, ndev, out);
   MSDE_CHECK_LAUNCH();
@@ -133,7 +176,7 @@ extern "C" int msde_cl_ebm_bwd(const float* X, const float* Y, const int* perm1,
                                float* gX, float* gY, const int* rows_dev, void* stream) {
   if (N <= 0 || D <= 0 || !X || !Y || !perm1 || !perm2 || !inv1 || !inv2 || !rows || !g_loss || !gX || !gY)
     return MSDE_EINVAL;
-  LAUNCH_ROWS(cl_bwd_kernel, N, D, X, Y, perm1, perm2, inv1, inv2, rows, g_loss, N, rows_dev, cols, tpr, invT,
+  LAUNCH_ROWS_PASSES(cl_bwd_kernel, N, D, X, Y, perm1, perm2, inv1, inv2, rows, g_loss, N, rows_dev, cols, tpr, invT,
               gX, gY);
   MSDE_CHECK_LAUNCH();
   return 0;

@@ -11,8 +11,14 @@ __device__ __forceinline__ typename VecT<V>::type bond_emb(const typename VecT<V
   return a;
 }
 
-template <int V>
-__global__ void gin_aggregate_fwd_kernel(const float* __restrict__ x, const float* __restrict__ tab,
+// Column passes.  A row of `cols` vectors is covered by tpr lanes in ceil(cols / tpr) passes (two at D = 300: 75 float4 over
+// 64 lanes).  P > 0: the pass count is a compile-time constant chosen by the host launch (LAUNCH_ROWS_PASSES), the edge
+// loop is the OUTER loop -- the row's indices are loaded once, not once per pass -- and the row loads of all passes are
+// issued before the first of them is used.  A lane past the last column reads column cols - 1 again and stores nothing.
+// P == 0: the run-time column loop, for a single pass, for wider rows and for V = 1.  Every output element is computed by the same lane with
+// the same additions in the same order either way.
+template <int V, int P>
+__global__ void __launch_bounds__(256) MSDE_ROW_WAVES gin_aggregate_fwd_kernel(const float* __restrict__ x, const float* __restrict__ tab,
                                          const int* __restrict__ codes, const float* __restrict__ eps,
                                          const int* __restrict__ rowptr, const int* __restrict__ src, int N, int cols,
                                          int tpr, float* __restrict__ out) {
@@ -26,6 +32,52 @@ __global__ void gin_aggregate_fwd_kernel(const float* __restrict__ x, const floa
   T* O = reinterpret_cast<T*>(out);
   float ope = 1.f + eps[0];
   int s0 = rowptr[i], s1 = rowptr[i + 1];
+  if constexpr (P > 0) {
+    int cc[P];
+    T xi[P], acc[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      cc[p] = min(lane + p * tpr, cols - 1);
+      xi[p] = X[(size_t)i * cols + cc[p]];
+      acc[p] = vzero<V>();
+    }
+    int e = s0;
+    for (; e + 1 < s1; e += 2) {      // two edges (2 neighbour rows + 6 table rows) per pass in flight, added in edge order
+      int j0 = src[e], j1 = src[e + 1];
+      int a0 = codes[3 * e], a1 = codes[3 * e + 1], a2 = codes[3 * e + 2];
+      int b0 = codes[3 * e + 3], b1 = codes[3 * e + 4], b2 = codes[3 * e + 5];
+      T x0[P], x1[P], t0[P], t1[P], t2[P], u0[P], u1[P], u2[P];
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const int c = cc[p];
+        x0[p] = X[(size_t)j0 * cols + c]; x1[p] = X[(size_t)j1 * cols + c];
+        t0[p] = Tb[(size_t)a0 * cols + c]; t1[p] = Tb[(size_t)a1 * cols + c]; t2[p] = Tb[(size_t)a2 * cols + c];
+        u0[p] = Tb[(size_t)b0 * cols + c]; u1[p] = Tb[(size_t)b1 * cols + c]; u2[p] = Tb[(size_t)b2 * cols + c];
+      }
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        acc[p] = vadd(acc[p], vrelu(vadd(x0[p], vadd(vadd(t0[p], t1[p]), t2[p]))));
+        acc[p] = vadd(acc[p], vrelu(vadd(x1[p], vadd(vadd(u0[p], u1[p]), u2[p]))));
+      }
+    }
+    for (; e < s1; ++e) {
+      int j0 = src[e];
+      int a0 = codes[3 * e], a1 = codes[3 * e + 1], a2 = codes[3 * e + 2];
+      T x0[P], t0[P], t1[P], t2[P];
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const int c = cc[p];
+        x0[p] = X[(size_t)j0 * cols + c];
+        t0[p] = Tb[(size_t)a0 * cols + c]; t1[p] = Tb[(size_t)a1 * cols + c]; t2[p] = Tb[(size_t)a2 * cols + c];
+      }
+#pragma unroll
+      for (int p = 0; p < P; ++p) acc[p] = vadd(acc[p], vrelu(vadd(x0[p], vadd(vadd(t0[p], t1[p]), t2[p]))));
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+      if (lane + p * tpr < cols) O[(size_t)i * cols + cc[p]] = vadd(vscale(xi[p], ope), acc[p]);
+    return;
+  }
   for (int c = lane; c < cols; c += tpr) {
     T acc = vzero<V>();
     int e = s0;
@@ -47,8 +99,8 @@ __global__ void gin_aggregate_fwd_kernel(const float* __restrict__ x, const floa
   }
 }
 
-template <int V>
-__global__ void gin_aggregate_bwd_x_kernel(const float* __restrict__ g, const float* __restrict__ x,
+template <int V, int P>             // P: column passes, as in gin_aggregate_fwd_kernel
+__global__ void __launch_bounds__(256) MSDE_ROW_WAVES gin_aggregate_bwd_x_kernel(const float* __restrict__ g, const float* __restrict__ x,
                                            const float* __restrict__ tab, const int* __restrict__ codes,
                                            const float* __restrict__ eps, const int* __restrict__ rowptr_s,
                                            const int* __restrict__ perm_s, const int* __restrict__ dst, int N,
@@ -64,6 +116,54 @@ __global__ void gin_aggregate_bwd_x_kernel(const float* __restrict__ g, const fl
   T* O = reinterpret_cast<T*>(g_x);
   float ope = 1.f + eps[0];
   int s0 = rowptr_s[j], s1 = rowptr_s[j + 1];
+  if constexpr (P > 0) {
+    int cc[P];
+    T xj[P], acc[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      cc[p] = min(lane + p * tpr, cols - 1);
+      xj[p] = X[(size_t)j * cols + cc[p]];
+      acc[p] = vscale(G[(size_t)j * cols + cc[p]], ope);
+    }
+    int s = s0;
+    for (; s + 1 < s1; s += 2) {      // two edges in flight (indices, then 2 gradient rows + 6 table rows per pass)
+      int e0 = perm_s[s], e1 = perm_s[s + 1];
+      int d0 = dst[e0], d1 = dst[e1];
+      int a0 = codes[3 * e0], a1 = codes[3 * e0 + 1], a2 = codes[3 * e0 + 2];
+      int b0 = codes[3 * e1], b1 = codes[3 * e1 + 1], b2 = codes[3 * e1 + 2];
+      T g0[P], g1[P], t0[P], t1[P], t2[P], u0[P], u1[P], u2[P];
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const int c = cc[p];
+        g0[p] = G[(size_t)d0 * cols + c]; g1[p] = G[(size_t)d1 * cols + c];
+        t0[p] = Tb[(size_t)a0 * cols + c]; t1[p] = Tb[(size_t)a1 * cols + c]; t2[p] = Tb[(size_t)a2 * cols + c];
+        u0[p] = Tb[(size_t)b0 * cols + c]; u1[p] = Tb[(size_t)b1 * cols + c]; u2[p] = Tb[(size_t)b2 * cols + c];
+      }
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        acc[p] = vadd(acc[p], vgate(g0[p], vadd(xj[p], vadd(vadd(t0[p], t1[p]), t2[p]))));
+        acc[p] = vadd(acc[p], vgate(g1[p], vadd(xj[p], vadd(vadd(u0[p], u1[p]), u2[p]))));
+      }
+    }
+    for (; s < s1; ++s) {
+      int e = perm_s[s];
+      int d0 = dst[e];
+      int a0 = codes[3 * e], a1 = codes[3 * e + 1], a2 = codes[3 * e + 2];
+      T g0[P], t0[P], t1[P], t2[P];
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const int c = cc[p];
+        g0[p] = G[(size_t)d0 * cols + c];
+        t0[p] = Tb[(size_t)a0 * cols + c]; t1[p] = Tb[(size_t)a1 * cols + c]; t2[p] = Tb[(size_t)a2 * cols + c];
+      }
+#pragma unroll
+      for (int p = 0; p < P; ++p) acc[p] = vadd(acc[p], vgate(g0[p], vadd(xj[p], vadd(vadd(t0[p], t1[p]), t2[p]))));
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+      if (lane + p * tpr < cols) O[(size_t)j * cols + cc[p]] = acc[p];
+    return;
+  }
   for (int c = lane; c < cols; c += tpr) {
     T xj = X[(size_t)j * cols + c];
     T acc = vscale(G[(size_t)j * cols + c], ope);
@@ -92,6 +192,8 @@ __global__ void gin_aggregate_bwd_x_kernel(const float* __restrict__ g, const fl
 // Forward: the layer input is h = max(z scale[c] + shift[c], 0 if relu) of the previous layer's second product z (its
 // outer BatchNorm, molecule_gnn_model.py:176-182): applied on the fly to every gathered row and to the node's own row,
 // which is also written out (h_out) -- the separate BatchNorm-apply launch of the layer disappears.
+// P: column passes of 64 lanes, as in gin_aggregate_fwd_kernel; the node's own row is requested with the first edge batch.
+template <int P>
 __global__ void __launch_bounds__(256)
 gin_aggregate_bn_fwd_kernel(const float* __restrict__ z, const float* __restrict__ scale, const float* __restrict__ shift,
                             int relu, const float* __restrict__ tab, const int* __restrict__ codes,
@@ -103,6 +205,63 @@ gin_aggregate_bn_fwd_kernel(const float* __restrict__ z, const float* __restrict
   const float4* Tb = reinterpret_cast<const float4*>(tab);
   const float ope = 1.f + eps[0];
   const int s0 = rowptr[i], s1 = rowptr[i + 1];
+  if constexpr (P > 0) {
+    int cc[P];
+    float4 sc[P], sh[P], zi[P], acc[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      cc[p] = min(lane + p * 64, cols - 1);
+      sc[p] = reinterpret_cast<const float4*>(scale)[cc[p]];
+      sh[p] = reinterpret_cast<const float4*>(shift)[cc[p]];
+      zi[p] = Z[(size_t)i * cols + cc[p]];
+      acc[p] = vzero4();
+    }
+    auto hval = [&](float4 zv, int p) {
+      float4 v = vfma(zv, sc[p], sh[p]);
+      return relu ? vrelu(v) : v;
+    };
+    int e = s0;
+    for (; e + 1 < s1; e += 2) {
+      const int j0 = src[e], j1 = src[e + 1];
+      const int a0 = codes[3 * e], a1 = codes[3 * e + 1], a2 = codes[3 * e + 2];
+      const int b0 = codes[3 * e + 3], b1 = codes[3 * e + 4], b2 = codes[3 * e + 5];
+      float4 z0[P], z1[P], t0[P], t1[P], t2[P], u0[P], u1[P], u2[P];
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const int c = cc[p];
+        z0[p] = Z[(size_t)j0 * cols + c]; z1[p] = Z[(size_t)j1 * cols + c];
+        t0[p] = Tb[(size_t)a0 * cols + c]; t1[p] = Tb[(size_t)a1 * cols + c]; t2[p] = Tb[(size_t)a2 * cols + c];
+        u0[p] = Tb[(size_t)b0 * cols + c]; u1[p] = Tb[(size_t)b1 * cols + c]; u2[p] = Tb[(size_t)b2 * cols + c];
+      }
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        acc[p] = vadd(acc[p], vrelu(vadd(hval(z0[p], p), vadd(vadd(t0[p], t1[p]), t2[p]))));
+        acc[p] = vadd(acc[p], vrelu(vadd(hval(z1[p], p), vadd(vadd(u0[p], u1[p]), u2[p]))));
+      }
+    }
+    for (; e < s1; ++e) {
+      const int j0 = src[e];
+      const int a0 = codes[3 * e], a1 = codes[3 * e + 1], a2 = codes[3 * e + 2];
+      float4 z0[P], t0[P], t1[P], t2[P];
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const int c = cc[p];
+        z0[p] = Z[(size_t)j0 * cols + c];
+        t0[p] = Tb[(size_t)a0 * cols + c]; t1[p] = Tb[(size_t)a1 * cols + c]; t2[p] = Tb[(size_t)a2 * cols + c];
+      }
+#pragma unroll
+      for (int p = 0; p < P; ++p) acc[p] = vadd(acc[p], vrelu(vadd(hval(z0[p], p), vadd(vadd(t0[p], t1[p]), t2[p]))));
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      if (lane + p * 64 < cols) {
+        const float4 hi = hval(zi[p], p);
+        reinterpret_cast<float4*>(h_out)[(size_t)i * cols + cc[p]] = hi;
+        reinterpret_cast<float4*>(out)[(size_t)i * cols + cc[p]] = vadd(vscale(hi, ope), acc[p]);
+      }
+    }
+    return;
+  }
   for (int c = lane; c < cols; c += 64) {
     const float4 sc = reinterpret_cast<const float4*>(scale)[c], sh = reinterpret_cast<const float4*>(shift)[c];
     auto hrow = [&](int j) {
@@ -209,8 +368,16 @@ extern "C" int msde_gin_aggregate_bn_fwd(const float* z, const float* scale, con
                                          int D, float* h_out, float* out, void* stream) {
   if (N < 0 || D <= 0 || D % 4 || !z || !scale || !shift || !tab || !eps || !rowptr || !h_out || !out) return MSDE_EINVAL;
   if (N == 0) return 0;
-  MSDE_LAUNCH(gin_aggregate_bn_fwd_kernel, dim3((N + 3) / 4), dim3(256), 0, as_stream(stream), z, scale, shift, relu, tab, codes,
-              eps, rowptr, src, N, D / 4, h_out, out);
+#define BN_FWD_LAUNCH(P)                                                                                                   \
+  MSDE_LAUNCH(gin_aggregate_bn_fwd_kernel<P>, dim3((N + 3) / 4), dim3(256), 0, as_stream(stream), z, scale, shift, relu, tab, \
+              codes, eps, rowptr, src, N, D / 4, h_out, out)
+  switch ((D / 4 + 63) / 64) {
+    case 1: BN_FWD_LAUNCH(1); break;
+    case 2: BN_FWD_LAUNCH(2); break;
+    case 3: BN_FWD_LAUNCH(3); break;
+    default: BN_FWD_LAUNCH(0);
+  }
+#undef BN_FWD_LAUNCH
   MSDE_CHECK_LAUNCH();
   return 0;
 }
@@ -315,7 +482,7 @@ extern "C" int msde_gin_aggregate_fwd(const float* x, const float* tab, const in
                                       const int* rowptr, const int* src, int N, int D, float* out, void* stream) {
   if (N < 0 || D <= 0 || !x || !tab || !eps || !rowptr || !out) return MSDE_EINVAL;
   if (N == 0) return 0;
-  LAUNCH_ROWS(gin_aggregate_fwd_kernel, N, D, x, tab, codes, eps, rowptr, src, N, cols, tpr, out);
+  LAUNCH_ROWS_PASSES(gin_aggregate_fwd_kernel, N, D, x, tab, codes, eps, rowptr, src, N, cols, tpr, out);
   MSDE_CHECK_LAUNCH();
   return 0;
 }
@@ -325,7 +492,7 @@ extern "C" int msde_gin_aggregate_bwd_x(const float* g, const float* x, const fl
                                         int N, int D, float* g_x, void* stream) {
   if (N < 0 || D <= 0 || !g || !x || !tab || !eps || !rowptr_s || !g_x) return MSDE_EINVAL;
   if (N == 0) return 0;
-  LAUNCH_ROWS(gin_aggregate_bwd_x_kernel, N, D, g, x, tab, codes, eps, rowptr_s, perm_s, dst, N, cols, tpr, g_x);
+  LAUNCH_ROWS_PASSES(gin_aggregate_bwd_x_kernel, N, D, g, x, tab, codes, eps, rowptr_s, perm_s, dst, N, cols, tpr, g_x);
   MSDE_CHECK_LAUNCH();
   return 0;
 }

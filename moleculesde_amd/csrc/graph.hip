@@ -767,7 +767,10 @@ extern "C" int msde_gather_rows(const float* X, const int* idx, int E, int D, fl
 // ------------------------------------------------------------------------------------------------
 // embedding sums (ogb AtomEncoder / BondEncoder / nn.Embedding)
 // ------------------------------------------------------------------------------------------------
-template <int V>
+// P > 0: ceil(cols / tpr) column passes and KB >= K as compile-time constants (msde_embedding_sum_fwd picks them): the K
+// codes of the row are loaded once and the table rows of all passes are in flight together; a lane past the last column
+// reads column cols - 1 again and stores nothing.  P == 0: the run-time column loop (wide rows, K > 16, V = 1).
+template <int V, int P, int KB>
 __global__ void embedding_sum_fwd_kernel(const float* __restrict__ tab, const int* __restrict__ codes, int N, int K,
                                          int cols, int tpr, float* __restrict__ out) {
   using T = typename VecT<V>::type;
@@ -777,6 +780,27 @@ __global__ void embedding_sum_fwd_kernel(const float* __restrict__ tab, const in
   if (i >= N) return;
   const T* Tb = reinterpret_cast<const T*>(tab);
   T* O = reinterpret_cast<T*>(out) + (size_t)i * cols;
+  if constexpr (P > 0) {
+    int cd[KB];
+#pragma unroll
+    for (int k = 0; k < KB; ++k) cd[k] = k < K ? codes[(size_t)i * K + k] : 0;
+    T v[P][KB];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      const int c = min(lane + p * tpr, cols - 1);
+#pragma unroll
+      for (int k = 0; k < KB; ++k) v[p][k] = k < K ? Tb[(size_t)cd[k] * cols + c] : vzero<V>();
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      T acc = v[p][0];                // left to right over k, as below
+#pragma unroll
+      for (int k = 1; k < KB; ++k)
+        if (k < K) acc = vadd(acc, v[p][k]);
+      if (lane + p * tpr < cols) O[lane + p * tpr] = acc;
+    }
+    return;
+  }
   for (int c = lane; c < cols; c += tpr) {
     // same left-to-right order as the reference's  x_embedding += emb_k(x[:,k])  (starts from 0); codes first,
     // then all table rows in flight (no code -> row chain per feature)
@@ -806,11 +830,19 @@ extern "C" int msde_embedding_sum_fwd(const float* tab, const int* codes, int N,
   if (N == 0) return 0;
   if (D % 4 == 0) {
     int cols = D / 4, tpr = pick_tpr(cols), rpb = 256 / tpr;
-    MSDE_LAUNCH(embedding_sum_fwd_kernel<4>, dim3((N + rpb - 1) / rpb), dim3(256), 0, as_stream(stream), tab,
-                       codes, N, K, cols, tpr, out);
+    const int passes = (cols + tpr - 1) / tpr;
+    // code bound KB: 1 (nn.Embedding), 9 (the ogb atom features), 16; at most 27 table vectors in flight per lane (more spill)
+#define ES_LAUNCH(P, KB)                                                                                               \
+  MSDE_LAUNCH((embedding_sum_fwd_kernel<4, P, KB>), dim3((N + rpb - 1) / rpb), dim3(256), 0, as_stream(stream), tab, codes, N, K, \
+              cols, tpr, out)
+    if (K > 16 || passes > 3 || (passes > 1 && K > 9)) ES_LAUNCH(0, 1);
+    else if (passes == 1) { if (K <= 1) ES_LAUNCH(1, 1); else if (K <= 9) ES_LAUNCH(1, 9); else ES_LAUNCH(1, 16); }
+    else if (passes == 2) { if (K <= 1) ES_LAUNCH(2, 1); else ES_LAUNCH(2, 9); }
+    else { if (K <= 1) ES_LAUNCH(3, 1); else ES_LAUNCH(3, 9); }
+#undef ES_LAUNCH
   } else {
     int cols = D, tpr = pick_tpr(cols), rpb = 256 / tpr;
-    MSDE_LAUNCH(embedding_sum_fwd_kernel<1>, dim3((N + rpb - 1) / rpb), dim3(256), 0, as_stream(stream), tab,
+    MSDE_LAUNCH((embedding_sum_fwd_kernel<1, 0, 1>), dim3((N + rpb - 1) / rpb), dim3(256), 0, as_stream(stream), tab,
                        codes, N, K, cols, tpr, out);
   }
   MSDE_CHECK_LAUNCH();

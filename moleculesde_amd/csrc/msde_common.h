@@ -130,3 +130,24 @@ __device__ __forceinline__ float msde_randn(unsigned long long seed, unsigned lo
     MSDE_LAUNCH(KERNEL<1>, dim3(((ROWS) + rpb - 1) / rpb), dim3(256), 0, as_stream(stream), __VA_ARGS__);    \
   }
 
+// the same for row kernels templated on <V, P>: P = the number of column passes, ceil(cols / tpr), as a compile-time
+// constant where it is 2 or 3 on the float4 path (two at D = 300), so that the kernel can request the row loads of all
+// passes at once; P = 0 = the kernel's run-time column loop (one pass, wider rows, V = 1)
+// Such a kernel's grid (one row per wave at 64 < cols) keeps at most 4 waves per SIMD resident on the step's shapes: the
+// compiler is told not to trade loads in flight for a higher occupancy than that.
+#define MSDE_ROW_WAVES __attribute__((amdgpu_waves_per_eu(1, 4)))
+#define LAUNCH_ROWS_P_(KERNEL, V, P, ROWS, ...)                                                                    \
+  MSDE_LAUNCH((KERNEL<V, P>), dim3(((ROWS) + rpb - 1) / rpb), dim3(256), 0, as_stream(stream), __VA_ARGS__)
+#define LAUNCH_ROWS_PASSES(KERNEL, ROWS, D, ...)                                                                   \
+  if ((D) % 4 == 0) {                                                                                              \
+    int cols = (D) / 4, tpr = pick_tpr(cols), rpb = 256 / tpr;                                                     \
+    switch ((cols + tpr - 1) / tpr) {                                                                              \
+      case 2: LAUNCH_ROWS_P_(KERNEL, 4, 2, ROWS, __VA_ARGS__); break;                                              \
+      case 3: LAUNCH_ROWS_P_(KERNEL, 4, 3, ROWS, __VA_ARGS__); break;                                              \
+      default: LAUNCH_ROWS_P_(KERNEL, 4, 0, ROWS, __VA_ARGS__);                                                    \
+    }                                                                                                              \
+  } else {                                                                                                         \
+    int cols = (D), tpr = pick_tpr(cols), rpb = 256 / tpr;                                                         \
+    LAUNCH_ROWS_P_(KERNEL, 1, 0, ROWS, __VA_ARGS__);                                                               \
+  }
+
