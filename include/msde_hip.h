@@ -886,7 +886,10 @@ int msde_mul_add_bwd(const float* g, const float* a, const float* b, long long n
  * G^2 score), x = x_mean + G noise.
  * step (device int64, may be NULL = row 0): the iteration counter -- the corrector uses row step[0] and then advances it, the
  * predictor of the same iteration uses row step[0] - 1: a captured iteration replays without any host work.
- * noise [n, 3], or NULL: N(0,1) draws from the counter generator keyed by (seed, row, corrector / predictor, element). */
+ * noise [n, 3], or NULL: N(0,1) draws from the counter generator: draw (row, stream, element) -- stream 0 the corrector's, 1 the
+ * predictor's -- is msde_randn(msde_mix64(seed, 2 row + stream), element), i.e. every (row, stream) has a FINALISED seed of its
+ * own (a seed that only adds a multiple of the generator's increment would make iteration r + 1 repeat the noise of
+ * iteration r one element further on). */
 int msde_pc_corrector(const float* out, const float* pos, const float* noise, const float* par, long long* step,
                       unsigned long long seed, int n, float snr, float scale_eps, float* x, float* x_mean, void* stream);
 int msde_pc_predictor(const float* out, const float* pos, const float* noise, const float* par, const long long* step,

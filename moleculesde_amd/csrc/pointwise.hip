@@ -724,8 +724,11 @@ __device__ __forceinline__ float pc_block_sum(float v, float* red) {
 // (ONE workgroup) reads step[0] as its row and then advances it; the predictor of the same iteration reads step[0] - 1.  With
 // step == NULL both use row 0 of `par_all` (the caller refreshes it).  noise == NULL: N(0,1) draws from the counter generator,
 // (seed, row, element) -> the same draw wherever it is asked for (the corrector needs its noise twice).
+// The seed of stream (row, stream_id) is the FINALISED msde_mix64(seed, 2 * row + stream_id): a seed that merely adds a multiple
+// of the generator's own increment makes the uniform counters a function of 2 * row + stream_id + 2 * i alone, so the noise of
+// iteration r + 1 at element i would be the noise of iteration r at element i + 1 (tests/rng_mirror.py, pc_draw_stream).
 __device__ __forceinline__ float pc_draw(const float* __restrict__ noise, unsigned long long seed, long long row, int stream_id, int i, int n3) {
-  return noise ? noise[i] : msde_randn(seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(2 * row + stream_id), (unsigned long long)i);
+  return noise ? noise[i] : msde_randn(msde_mix64(seed, (unsigned long long)(2 * row + stream_id)), (unsigned long long)i);
 }
 
 __global__ void __launch_bounds__(1024)

@@ -48,7 +48,9 @@ def position_PC_generation(score_model, representation, data, num_steps=1000, sn
     inside) is captured into a hipGraph after two eager warm-up iterations and replayed.  On the fused path (one shared
     diffusion time, one corrector step) the replay needs nothing from the host: the iteration counter and the noise live in
     the two update kernels (noise_seed: their seed; None = drawn from torch's generator), and iters_per_graph iterations
-    share one graph launch.  torch_noise=True: the noise comes
+    share one graph launch.  The draw of iteration `row`, corrector (stream 0) or predictor (stream 1), flat coordinate i is
+    msde_randn(msde_mix64(noise_seed, 2 * row + stream), i) (csrc/pointwise.hip pc_draw; host mirror: tests/rng_mirror.py): every
+    (row, stream) has a finalised seed of its own, so no two iterations share a uniform.  torch_noise=True: the noise comes
     from torch.randn_like as in the operator path (parity tests: same generator state => same trajectory)."""
     sde = score_model.sde_pos
     n = representation.size(0)
@@ -207,7 +209,8 @@ def position_PC_generation_grouped(score_model, representation, data, group_ptr,
 
     Same structure as position_PC_generation (table once, two eager warm-up iterations, capture, replay) on
     msde_pc_corrector_grouped / msde_pc_predictor_grouped; group_seeds: one noise seed per group (None: drawn from the device's
-    torch generator) -- group g walks the trajectory of position_PC_generation(noise_seed=group_seeds[g]) on that group alone.
+    torch generator) -- group g walks the trajectory of position_PC_generation(noise_seed=group_seeds[g]) on that group alone
+    (its draws: msde_randn(msde_mix64(group_seeds[g], 2 * row + stream), coordinate counted from the group's first)).
     The operator path (CPU, n_corrector_steps != 1) draws its noise from torch's generator, as position_PC_generation's does."""
     sde = score_model.sde_pos
     n = representation.size(0)
