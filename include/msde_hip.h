@@ -1118,6 +1118,37 @@ int msde_dataset_gather_batch_masked(const int* x, const float* pos, const int* 
                                      int off_attr, int off_atoms, int off_bonds, int total_words, const unsigned* keep,
                                      const unsigned* mol_rows, int* blob, unsigned* ext_in, int* err, void* stream);
 
+/* ------------------------------------------------------------------ conformer evaluation --- */
+/* COV / MAT scores of generated conformers (the evaluation of the 2D->3D sampler's output; csrc/conformer_rmsd.hip).
+ * A launch holds G molecules; molecule g has n atoms, R reference and K generated conformers.
+ *   ref_pos [sum R n, 3], gen_pos [sum K n, 3] fp32, conformer-major within a molecule (the layout of `pos_gen`).
+ *   mol [G][8] int64 (device): n, R, K, ref_row0, gen_row0 (row of the molecule's first reference / generated conformer in
+ *     ref_pos / gen_pos), out_off (element of its R x K block in rmsd), mask_off (its first atom in atom_mask), conf_off
+ *     (= sum over the molecules before it of R + K: its first conformer record; ascending, mol[0] has 0).  All >= 1 / >= 0,
+ *     inside the buffers: the host's duty, the kernels trust the table.
+ *   tiles [n_tiles][3] int32 (device): molecule, first reference, first generated conformer of an 8 x 8 tile of pairs; the
+ *     tiles of a molecule cover its R x K pairs once (ceil(R / 8) * ceil(K / 8) of them).
+ *   atom_mask [sum n] uint8 or NULL (all atoms): atoms with 0 are left out of every sum, for all conformers of the molecule.
+ *   prep [n_conf][5] fp64 workspace, n_conf = sum (R + K): per conformer centroid, squared norm about it, kept atoms.
+ * msde_conf_rmsd_matrix: rmsd[out_off + r K + k] (fp64) = min over proper rotations (det = +1, no reflection) and
+ *   translations of sqrt(mean over the kept atoms of |Q (x_a - c_x) - (y_a - c_y)|^2), x = reference r, y = generated k,
+ *   atoms paired in stored order (plain Kabsch: no symmetry permutation, an upper bound of a symmetry-aware best RMSD).
+ *   fp64 throughout, centred before any product; largest eigenvalue of Horn's 4 x 4 matrix by a fixed number of Jacobi
+ *   sweeps; sqrt(max(0, (G_x + G_y - 2 lambda) / n)).  Fixed summation order, no atomics: a pair's value is a function of its
+ *   two conformers and the mask alone, bitwise.  A conformer with a non-finite kept coordinate (or a molecule with no kept
+ *   atom) gives NaN in its whole row / column and touches nothing else.  n_tiles or n_conf / 4 above 2^31 - 1: MSDE_EUNSUP.
+ * msde_conf_cov_mat: per molecule, over its block of rmsd with NaN read as +inf: rowmin_r = min_k, colmin_k = min_r, written
+ *   to conf_min [n_conf] (the molecule's R row minima, then its K column minima, at conf_off);
+ *   stats [G][2 T + 3] fp64 = COV-R [T] (#{r: rowmin_r <= thresholds[t]} / R), COV-P [T] (#{k: colmin_k <= thresholds[t]} / K,
+ *   non-finite generated conformers stay in the denominator), MAT-R (mean_r rowmin_r), MAT-P (mean of the finite colmin_k),
+ *   the number of finite colmin_k (generated conformers with a finite RMSD to some reference).  Means in index order.  None
+ *   finite: COV 0, both MAT NaN, count 0.  thresholds [T] fp64 (device). */
+int msde_conf_rmsd_matrix(const float* ref_pos, const float* gen_pos, const long long* mol, int G, const int* tiles,
+                          long long n_tiles, const unsigned char* atom_mask, long long n_conf, double* prep, double* rmsd,
+                          void* stream);
+int msde_conf_cov_mat(const double* rmsd, const long long* mol, int G, const double* thresholds, int T, double* conf_min,
+                      double* stats, void* stream);
+
 /* ------------------------------------------------------------------ optimiser -------------- */
 /* torch.optim.Adam step over a flat parameter buffer with per-element lr via segment table —
  * examples/pretrain_MoleculeSDE.py:331-337,156.  seg_end[S] (exclusive ends), seg_lr[S].

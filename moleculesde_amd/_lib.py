@@ -191,6 +191,8 @@ SIGNATURES = {
     "msde_escore_mol_score_scratch_floats": [I],
     "msde_escore_mol_slab_floats": [],
     "msde_escore_mol_bwd": [P, P, P, I, P, P, I, P, P, P, P, P, I, I, I, I, I, I, F, F, ULL, P, F, F, P, P, P, P, I, P, P],
+    "msde_conf_rmsd_matrix": [P, P, P, I, P, LL, P, LL, P, P, P],
+    "msde_conf_cov_mat": [P, P, I, P, I, P, P, P],
     "msde_chunk_elems": [],
     "msde_gather_chunks": [P, I, P, P],
     "msde_adam_chunks": [P, P, I, P, P, P, P, P, I, F, F, F, F, F, P],
