@@ -1148,6 +1148,28 @@ int msde_conf_rmsd_matrix(const float* ref_pos, const float* gen_pos, const long
                           void* stream);
 int msde_conf_cov_mat(const double* rmsd, const long long* mol, int G, const double* thresholds, int T, double* conf_min,
                       double* stats, void* stream);
+/* msde_conf_rmsd_matrix_sym: the symmetry-aware RMSD (what rdkit's GetBestRMS reports, without chirality): every argument
+ *   of msde_conf_rmsd_matrix as there, and
+ *   sym [G][2] int64 (device): P >= 1 permutations of the molecule, perm_off (element of its first one in perms);
+ *   perms [sum P n] int32 (device): row p of molecule g = perms[perm_off + p n .. + n], molecule-local atom indices;
+ *     perm[p][a] is the REFERENCE atom paired with atom a of the generated conformer.  Every row maps the kept atoms onto
+ *     the kept atoms one to one (entries of atoms the mask leaves out are not read): the host's duty, as for `mol`.
+ *   lds_atoms, 0 .. 160: molecules of at most this many atoms have the tile's 8 + 8 centred conformers staged in LDS
+ *     (16 (3 lds_atoms + 1) doubles of dynamic LDS per workgroup, the same for the whole launch), larger ones read global
+ *     memory; the two paths give the same bits.  Outside the range: MSDE_EINVAL.
+ *   rmsd[out_off + r K + k] = min over p < P of the pair formula above with S_p = sum over the kept atoms a of
+ *   (x_{perm[p][a]} - c_x)(y_a - c_y)^T: kept atoms, centroids, G_x and G_y are those of the preparation kernel (a
+ *   permutation of the kept atoms does not move them), so the minimum of the RMSD is the formula at the largest lambda.
+ *   One workgroup per 8 x 8 tile (the same tile table); a wave takes the permutations p = w, w + 4, ... one at a time for
+ *   the 64 pairs, one alignment per lane, atoms in index order.  No workspace and no permutation-chunk column: a molecule's
+ *   P alignments of a tile run on its one workgroup, 4 permutations at a time.  No atomics; an alignment's value is a
+ *   function of its (x, y, perm[p], mask) alone and the maximum is exact, so the result does not depend on the order of
+ *   the rows, on what else is in the launch, or on lds_atoms, bitwise.  With P = 1 and the identity it agrees with
+ *   msde_conf_rmsd_matrix to round-off (another summation order), not bitwise.  NaN rules, the absence of reflections and
+ *   the MSDE_EUNSUP cases are those of msde_conf_rmsd_matrix. */
+int msde_conf_rmsd_matrix_sym(const float* ref_pos, const float* gen_pos, const long long* mol, int G, const int* tiles,
+                              long long n_tiles, const unsigned char* atom_mask, long long n_conf, const long long* sym,
+                              const int* perms, int lds_atoms, double* prep, double* rmsd, void* stream);
 
 /* ------------------------------------------------------------------ optimiser -------------- */
 /* torch.optim.Adam step over a flat parameter buffer with per-element lr via segment table —

@@ -192,6 +192,7 @@ SIGNATURES = {
     "msde_escore_mol_slab_floats": [],
     "msde_escore_mol_bwd": [P, P, P, I, P, P, I, P, P, P, P, P, I, I, I, I, I, I, F, F, ULL, P, F, F, P, P, P, P, I, P, P],
     "msde_conf_rmsd_matrix": [P, P, P, I, P, LL, P, LL, P, P, P],
+    "msde_conf_rmsd_matrix_sym": [P, P, P, I, P, LL, P, LL, P, P, I, P, P, P],
     "msde_conf_cov_mat": [P, P, I, P, I, P, P, P],
     "msde_chunk_elems": [],
     "msde_gather_chunks": [P, I, P, P],

@@ -16,6 +16,8 @@
 //       of 16 pairs, one pair at a time: lane-strided partial sums over the atoms (any n), then an xor butterfly over the 64
 //       lanes -- a fixed order, no atomics, so a pair's value depends on its own two conformers only.  The 64 S land in LDS
 //       and the first wave solves them one pair per lane (the serial eigen-solve keeps 64 lanes busy, not one).
+//   (2s) cr_sym_kernel: the symmetry-aware RMSD, the minimum of the above over a table of atom permutations per molecule
+//       (the automorphisms of its graph, enumerated on the host): see the comment above the kernel.
 // Eigen-solve: CR_SWEEPS cyclic Jacobi sweeps on the 4 x 4 (eigenvalues only).  A fixed count, no convergence test: repeated
 // eigenvalues (identical, collinear, planar conformers, one or two atoms) leave it nothing to rotate and are harmless.
 // A conformer with a non-finite kept coordinate has G = NaN, and every pair it takes part in is written as NaN.
@@ -187,6 +189,117 @@ __global__ void __launch_bounds__(256) cr_pair_kernel(const float* __restrict__ 
   }
 }
 
+// ---- (2s) symmetry-aware: one 8 x 8 tile of pairs per workgroup, every permutation of the molecule --------------------------
+// rmsd = min over the P rows of the molecule's permutation table of the pair formula with S_p = sum_a x_{perm[p][a]} y_a^T
+// (centred, kept atoms a): the count, the centroids and G do not move under a permutation of the kept atoms, so the records
+// of cr_prep_kernel serve every p and min_p rmsd = the formula at max_p lambda.
+// Layout: one ALIGNMENT (pair, p) per lane, serial over the atoms.  A wave takes one p at a time for all 64 pairs of the
+// tile (wave w: p = w, w + 4, ...), so perm[p][a] is the same for the whole wave: 64 entries are fetched by one coalesced
+// load and handed out by v_readlane.  The tile's 8 + 8 conformers are centred once, in fp64, into LDS ([16][stride] doubles,
+// stride = 3 n made odd: the 4 reference and 8 generated rows a 32-lane group reads fall on different banks); a molecule of
+// more than lds_atoms atoms reads the fp32 coordinates from global memory and centres on the fly -- (double)x - c is the
+// same number either way, so the two paths agree bitwise.  Nothing crosses lanes until the maximum of lambda: each lane keeps
+// its own over the p of its wave, four values per pair meet in LDS.  fmax is exact, so the order of the table, the split of
+// the p over the waves and the path do not show in the result; the sum over the atoms runs a = 0, 1, ... for every p.
+// A partial tile's missing conformers are clamped to the last valid one (computed, not written): no lane idles or diverges.
+#define CS_LDS_ATOMS 160           // 16 (3 * 160 + 1) doubles = 61 568 bytes + 2 048 of lambda: inside the 64 KiB a launch may ask
+
+__device__ __forceinline__ int cs_stride(int nl) { return (3 * nl) | 1; }
+
+template <bool LDS>
+__device__ __forceinline__ void cs_accumulate(double (&s)[9], const double* __restrict__ xs, const double* __restrict__ ys,
+                                              const float* __restrict__ xg, const float* __restrict__ yg,
+                                              const double (&cx)[3], const double (&cy)[3], long long pa, long long a) {
+  double x0, x1, x2, y0, y1, y2;
+  if (LDS) {                                                 // n <= CS_LDS_ATOMS here: 32-bit offsets
+    const int ip = 3 * (int)pa, ia = 3 * (int)a;
+    x0 = xs[ip]; x1 = xs[ip + 1]; x2 = xs[ip + 2];
+    y0 = ys[ia]; y1 = ys[ia + 1]; y2 = ys[ia + 2];
+  } else {
+    x0 = (double)xg[3 * pa] - cx[0]; x1 = (double)xg[3 * pa + 1] - cx[1]; x2 = (double)xg[3 * pa + 2] - cx[2];
+    y0 = (double)yg[3 * a] - cy[0]; y1 = (double)yg[3 * a + 1] - cy[1]; y2 = (double)yg[3 * a + 2] - cy[2];
+  }
+  s[0] += x0 * y0; s[1] += x0 * y1; s[2] += x0 * y2;
+  s[3] += x1 * y0; s[4] += x1 * y1; s[5] += x1 * y2;
+  s[6] += x2 * y0; s[7] += x2 * y1; s[8] += x2 * y2;
+}
+
+// the largest lambda of this lane's pair over the permutations p = wave, wave + 4, ... < P
+template <bool LDS>
+__device__ __forceinline__ double cs_best_lambda(const double* __restrict__ xs, const double* __restrict__ ys,
+                                                 const float* __restrict__ xg, const float* __restrict__ yg,
+                                                 const double (&cx)[3], const double (&cy)[3],
+                                                 const unsigned char* __restrict__ mk, const int* __restrict__ pm,
+                                                 long long n, long long P, int wave, int lane) {
+  double best = -__longlong_as_double(0x7ff0000000000000ll);
+  for (long long p = wave; p < P; p += 4) {
+    const int* row = pm + p * n;
+    double s[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) s[e] = 0.0;
+    for (long long a0 = 0; a0 < n; a0 += 64) {
+      const long long al = a0 + lane;
+      const int mine = (al < n && (!mk || mk[al])) ? row[al] : -1;      // -1: past the end, or an atom the mask leaves out
+      const int cnt = (int)(n - a0 < 64 ? n - a0 : 64);
+      for (int j = 0; j < cnt; ++j) {
+        const int pa = __builtin_amdgcn_readlane(mine, j);              // the same for the whole wave
+        if (pa >= 0) cs_accumulate<LDS>(s, xs, ys, xg, yg, cx, cy, pa, a0 + j);
+      }
+    }
+    best = fmax(best, cr_horn_lambda(s));
+  }
+  return best;
+}
+
+__global__ void __launch_bounds__(256) cr_sym_kernel(const float* __restrict__ ref_pos, const float* __restrict__ gen_pos,
+                                                     const long long* __restrict__ mol, const int* __restrict__ tiles,
+                                                     const unsigned char* __restrict__ mask,
+                                                     const long long* __restrict__ sym, const int* __restrict__ perms,
+                                                     int lds_atoms, const double* __restrict__ prep,
+                                                     double* __restrict__ out) {
+  extern __shared__ double cs_pos[];                         // [16][cs_stride(lds_atoms)]: the tile's centred conformers
+  __shared__ double sL[4 * CR_PAIRS];                        // the best lambda of each wave, per pair
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int* tl = tiles + (size_t)blockIdx.x * 3;
+  const long long* m = mol + (size_t)tl[0] * CR_MOL;
+  const long long n = m[0], R = m[1], K = m[2], r0 = tl[1], k0 = tl[2];
+  const long long P = sym[(size_t)tl[0] * 2], perm_off = sym[(size_t)tl[0] * 2 + 1];
+  const unsigned char* mk = mask ? mask + m[6] : nullptr;
+  const bool in_lds = n <= (long long)lds_atoms;             // the same for the whole workgroup
+  const int stride = cs_stride(lds_atoms);
+  if (in_lds) {
+    const int per = 3 * (int)n;
+    for (int i = threadIdx.x; i < 16 * per; i += 256) {
+      const int c = i / per, e = i - c * per, d = e % 3;
+      const long long j = c < 8 ? (r0 + c < R ? r0 + c : R - 1) : (k0 + c - 8 < K ? k0 + c - 8 : K - 1);
+      const float* src = c < 8 ? ref_pos + 3 * (m[3] + j * n) : gen_pos + 3 * (m[4] + j * n);
+      const double* rec = prep + (size_t)(m[7] + (c < 8 ? j : R + j)) * CR_REC;
+      cs_pos[c * stride + e] = (double)src[e] - rec[d];
+    }
+  }
+  __syncthreads();
+  const long long r = r0 + (lane >> 3) < R ? r0 + (lane >> 3) : R - 1, k = k0 + (lane & 7) < K ? k0 + (lane & 7) : K - 1;
+  const double* px = prep + (size_t)(m[7] + r) * CR_REC;
+  const double* py = prep + (size_t)(m[7] + R + k) * CR_REC;
+  const double cx[3] = {px[0], px[1], px[2]}, cy[3] = {py[0], py[1], py[2]};
+  const float* xg = ref_pos + 3 * (m[3] + r * n);
+  const float* yg = gen_pos + 3 * (m[4] + k * n);
+  const double* xs = cs_pos + (int)(r - r0) * stride;
+  const double* ys = cs_pos + (8 + (int)(k - k0)) * stride;
+  const int* pm = perms + perm_off;
+  const double best = in_lds ? cs_best_lambda<true>(xs, ys, xg, yg, cx, cy, mk, pm, n, P, wave, lane)
+                             : cs_best_lambda<false>(xs, ys, xg, yg, cx, cy, mk, pm, n, P, wave, lane);
+  sL[wave * CR_PAIRS + lane] = best;
+  __syncthreads();
+  if (wave == 0 && r0 + (lane >> 3) < R && k0 + (lane & 7) < K) {
+    const double lam = fmax(fmax(sL[lane], sL[CR_PAIRS + lane]), fmax(sL[2 * CR_PAIRS + lane], sL[3 * CR_PAIRS + lane]));
+    const double e0 = px[3] + py[3];
+    double v = sqrt(fmax(0.0, (e0 - 2.0 * lam) / px[4]));
+    if (!isfinite(e0)) v = __longlong_as_double(0x7ff8000000000000ll);     // one of the two conformers is not finite
+    out[m[5] + r * K + k] = v;
+  }
+}
+
 // ---- COV / MAT: one workgroup per molecule ----------------------------------------------------------------------------------
 // conf_min [n_conf] in the order of the conformer records: a molecule's R row minima, then its K column minima (NaN entries
 // count as +inf).  stats [G][2 T + 3] = COV-R [T], COV-P [T], MAT-R, MAT-P, finite generated conformers.
@@ -251,6 +364,24 @@ extern "C" int msde_conf_rmsd_matrix(const float* ref_pos, const float* gen_pos,
   MSDE_CHECK_LAUNCH();
   MSDE_LAUNCH(cr_pair_kernel, dim3((unsigned)n_tiles), dim3(256), 0, as_stream(stream), ref_pos, gen_pos, mol, tiles,
               atom_mask, (const double*)prep, rmsd);
+  MSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int msde_conf_rmsd_matrix_sym(const float* ref_pos, const float* gen_pos, const long long* mol, int G,
+                                         const int* tiles, long long n_tiles, const unsigned char* atom_mask, long long n_conf,
+                                         const long long* sym, const int* perms, int lds_atoms, double* prep, double* rmsd,
+                                         void* stream) {
+  if (!ref_pos || !gen_pos || !mol || !tiles || !sym || !perms || !prep || !rmsd || G <= 0 || n_tiles <= 0 ||
+      n_conf < 2 * (long long)G || lds_atoms < 0 || lds_atoms > CS_LDS_ATOMS)
+    return MSDE_EINVAL;
+  if (n_tiles > 0x7fffffffll || (n_conf + 3) / 4 > 0x7fffffffll) return MSDE_EUNSUP;
+  MSDE_LAUNCH(cr_prep_kernel, dim3((unsigned)((n_conf + 3) / 4)), dim3(256), 0, as_stream(stream), ref_pos, gen_pos, mol, G,
+              atom_mask, n_conf, prep);
+  MSDE_CHECK_LAUNCH();
+  const size_t lds = lds_atoms > 0 ? (size_t)16 * ((3 * lds_atoms) | 1) * sizeof(double) : 0;
+  MSDE_LAUNCH(cr_sym_kernel, dim3((unsigned)n_tiles), dim3(256), lds, as_stream(stream), ref_pos, gen_pos, mol, tiles,
+              atom_mask, sym, perms, lds_atoms, (const double*)prep, rmsd);
   MSDE_CHECK_LAUNCH();
   return 0;
 }
