@@ -1171,6 +1171,48 @@ int msde_conf_rmsd_matrix_sym(const float* ref_pos, const float* gen_pos, const 
                               long long n_tiles, const unsigned char* atom_mask, long long n_conf, const long long* sym,
                               const int* perms, int lds_atoms, double* prep, double* rmsd, void* stream);
 
+/* ------------------------------------------------------------------ 2D graph evaluation ---- */
+/* Decoding and scoring of the 3D->2D sampler's output (class scores x, adjacency values around `bond type + 1`) against the
+ * graph the 3D input came from; csrc/graph2d_eval.hip.  A launch holds G molecules; molecule g has n atoms and K samples.
+ *   x_gen [sum K n ncls], adj_gen [sum K n n] fp32, sample-major within a molecule; z [sum n] int32 target class in
+ *   [0, ncls); adj_tgt [sum n n] uint8 target bond code 0..5 (0 none, 1 single, 2 double, 3 triple, 4 aromatic, 5 misc;
+ *   symmetric, only i < j is read); atom_flag [sum n] uint8: an atom with 0 is masked like padding -- none of its scores or
+ *   pairs is loaded; max_valence2 [ncls] uint8 or NULL: cap of an atom's bond-order sum in HALF-bond units by DECODED class,
+ *   0 = unchecked (single 2, double 4, triple 6, aromatic 3, misc 2).
+ *   mol [G][8] int64 (device): n, K, x_off, adj_off (first element of the molecule in x_gen / adj_gen), atom_off (first atom
+ *     in z / atom_flag), tgt_off (first element in adj_tgt), samp_off (= sum of K before it: its first sample record;
+ *     ascending, mol[0] has 0), sig_off (first byte of its signatures).  The host's duty, as for the conformer tables.
+ *   n_samples = sum K; n_max = the largest n (the host's bound; above 1024: MSDE_EUNSUP, as are ncls > 256 and
+ *     n_samples > 2^31 - 1); max_bond in 1..5 (else MSDE_EINVAL).
+ * msde_graph2d_decode, one workgroup per sample.  Per flagged atom the class = argmax of its ncls scores, the lowest index
+ *   among equal values.  Per pair i < j of flagged atoms v = 0.5 ((double)a_ij + (double)a_ji), q = clamp(floor(v + 0.5), 0,
+ *   max_bond).  A NaN or +-inf on a flagged atom's score row or on either element of a flagged pair makes the sample
+ *   NON-FINITE.  Outputs:
+ *   sig: per sample n + n (n - 1) / 2 bytes at sig_off + k (n + n (n - 1) / 2): the classes [n], then the codes of the
+ *     row-major upper triangle; 0 on unflagged entries; all 0 for a non-finite sample.
+ *   counts [n_samples][9] int32 (finite sample / non-finite sample): finite 1 / 0; atoms_correct / 0; tp, fp (bond existence
+ *     q > 0 against t > 0 over the flagged pairs) / 0, 0; fn / the number of true bonds; order_correct (t > 0 and q == t) / 0;
+ *     exact (every flagged atom and pair equal) / 0; components (connected components of the decoded graph on the flagged
+ *     atoms, min-label propagation in LDS swept until nothing changes) / 0; valence_violations (flagged atoms whose
+ *     bond-order sum exceeds max_valence2[decoded class]) / 0.
+ *   adj_l1 [n_samples] fp64: sum over the flagged pairs i < j of |v - t| / NaN.
+ *   Fixed summation order, no atomics: a sample's outputs are a function of the sample and its molecule's targets alone.
+ * msde_graph2d_summary, one workgroup per molecule, on the outputs of the decode call.
+ *   first [n_samples] uint8: 1 for a finite sample whose signature equals that of no earlier finite sample of its molecule
+ *     (bytes compared, no hashing).
+ *   stats [G][11] fp64, each of 0..7 a mean over all K samples in index order with non-finite samples adding 0: atom accuracy
+ *     (atoms_correct / flagged atoms), bond precision tp / (tp + fp), recall tp / (tp + fn), F1 2 tp / (2 tp + fp + fn),
+ *     bond-order accuracy order_correct / tp -- every one of these ratios is 1 where its denominator is 0 -- exact-match
+ *     rate, valid rate (finite, components == 1, no valence violation), unique fraction (#first / K); then [8] any_exact
+ *     (1 if some sample is exact), [9] the mean over the finite samples of adj_l1 per flagged pair (NaN without a finite
+ *     sample), [10] the number of finite samples. */
+int msde_graph2d_decode(const float* x_gen, const float* adj_gen, const int* z, const unsigned char* adj_tgt,
+                        const unsigned char* atom_flag, const unsigned char* max_valence2, const long long* mol, int G,
+                        long long n_samples, int n_max, int ncls, int max_bond, unsigned char* sig, int* counts, double* adj_l1,
+                        void* stream);
+int msde_graph2d_summary(const unsigned char* sig, const int* counts, const double* adj_l1, const unsigned char* atom_flag,
+                         const long long* mol, int G, unsigned char* first, double* stats, void* stream);
+
 /* ------------------------------------------------------------------ optimiser -------------- */
 /* torch.optim.Adam step over a flat parameter buffer with per-element lr via segment table —
  * examples/pretrain_MoleculeSDE.py:331-337,156.  seg_end[S] (exclusive ends), seg_lr[S].

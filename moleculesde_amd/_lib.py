@@ -194,6 +194,8 @@ SIGNATURES = {
     "msde_conf_rmsd_matrix": [P, P, P, I, P, LL, P, LL, P, P, P],
     "msde_conf_rmsd_matrix_sym": [P, P, P, I, P, LL, P, LL, P, P, I, P, P, P],
     "msde_conf_cov_mat": [P, P, I, P, I, P, P, P],
+    "msde_graph2d_decode": [P, P, P, P, P, P, P, I, LL, I, I, I, P, P, P, P],
+    "msde_graph2d_summary": [P, P, P, P, P, I, P, P, P],
     "msde_chunk_elems": [],
     "msde_gather_chunks": [P, I, P, P],
     "msde_adam_chunks": [P, P, I, P, P, P, P, P, I, F, F, F, F, F, P],
