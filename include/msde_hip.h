@@ -730,6 +730,27 @@ int msde_dense_pc_corrector(const msde_dense_pc_params* p, const float* G2, int 
 /* reverse-diffusion predictor: x_mean = x - (f(x) - G^2 score), x = x_mean + G z. */
 int msde_dense_pc_predictor(const msde_dense_pc_params* p, const float* G2, int F2, const float* w2, const float* b2,
                             const float* OUT, void* stream);
+/* The same sampler for several test-set molecules per trajectory (csrc/dense_pc_grouped.hip).  A group is a contiguous range
+ * of the batch's molecules, [group_ptr[g], group_ptr[g + 1]) (the replicas of one molecule): group_ptr [G + 1] over MOLECULES,
+ * from 0 to p->B, no empty range (the caller checks the table; a workgroup whose molecule it does not place does nothing).
+ * Groups share the schedule and step [2] and nothing else: the corrector's mean norms run over the group's own molecules
+ * (ascending, / (float)K_g), and the counter noise of molecule b is keyed by (group_seed[g], iteration, draw, adj / x,
+ * b - group_ptr[g], element) -- p->seed is not read -- so group g computes what the calls above compute for that group
+ * alone with seed = group_seed[g].  Injected draws keep their padded offsets with the global molecule index.  group_bad [G]:
+ * zeroed by init, set to 1 by the predictor when a written x_mean / adj_mean value of the group is not finite, never cleared.
+ * Limits and return codes as above. */
+typedef struct msde_dense_pc_groups {
+  const int* group_ptr;
+  const unsigned long long* group_seed;
+  int* group_bad;
+  int G;
+} msde_dense_pc_groups;
+int msde_dense_pc_init_grouped(const msde_dense_pc_params* p, const msde_dense_pc_groups* gr, const float* adj_given,
+                               void* stream);
+int msde_dense_pc_corrector_grouped(const msde_dense_pc_params* p, const msde_dense_pc_groups* gr, const float* G2, int F2,
+                                    const float* w2, const float* b2, const float* OUT, void* stream);
+int msde_dense_pc_predictor_grouped(const msde_dense_pc_params* p, const msde_dense_pc_groups* gr, const float* G2, int F2,
+                                    const float* w2, const float* b2, const float* OUT, void* stream);
 
 /* ------------------------------------------------------------------ contrastive loss ------- */
 /* do_CL('EBM_node_dot_prod') in both directions + dual_CL — examples/util.py:52-68,76-79.

@@ -111,6 +111,9 @@ SIGNATURES = {
     "msde_dense_pc_init": [P, P, P],
     "msde_dense_pc_corrector": [P, P, I, P, P, P, P],
     "msde_dense_pc_predictor": [P, P, I, P, P, P, P],
+    "msde_dense_pc_init_grouped": [P, P, P, P],
+    "msde_dense_pc_corrector_grouped": [P, P, P, I, P, P, P, P],
+    "msde_dense_pc_predictor_grouped": [P, P, P, I, P, P, P, P],
     "msde_plan_build": [P, I, P, P, P, P, P, P, P, I, I, I, I, I, I, I] + [P] * 23 + [P],
     "msde_plan_build_ext": [P, I, P, P, P, P, P, P, P, I, I, I, I, I, I, I] + [P] * 23 + [P, P],
     "msde_plan_row_lists": [P, P, I, I, P, P, P, P],
@@ -235,6 +238,11 @@ class DensePcParams(ctypes.Structure):
                                  "nzp_x")] + \
         [("seed", ULL)] + [(n, I) for n in ("B", "Nm", "ncls", "n_steps", "S", "iters", "F", "ldxc")] + \
         [("snr", F), ("scale_eps", F)]
+
+
+class DensePcGroups(ctypes.Structure):
+    """msde_dense_pc_groups of include/msde_hip.h."""
+    _fields_ = [("group_ptr", P), ("group_seed", P), ("group_bad", P), ("G", I)]
 
 
 class EdgeLayerParams(ctypes.Structure):

@@ -305,27 +305,52 @@ def record_from_sample(data, x, adj):
     return rec
 
 
+def launch_chunks(start, end, num_molecules, molecules_per_launch):
+    """The launches of generate_graphs_from_testset: the molecule indices of molecules[start:end] (clamped to the set) cut
+    into consecutive chunks of molecules_per_launch, the last one possibly shorter."""
+    per = int(molecules_per_launch)
+    if per < 1:
+        raise ValueError("molecules_per_launch must be at least 1")
+    start, end = max(0, int(start)), min(int(end), int(num_molecules))
+    return [list(range(lo, min(lo + per, end))) for lo in range(start, end, per)]
+
+
 def generate_graphs_from_testset(molecules, model_3d, sde_model, num_repeat=10, start=0, end=100, noise_seed=None, out_path=None,
-                                 **kw):
-    """The 3D->2D inference script's test-set loop: num_repeat samples for every molecule of molecules[start:end], one
-    sampler_3d2d.generate_2d_from_3d call per molecule (the sampler as it is; several molecules per trajectory are not built).
-    A molecule's noise seed is sampler.group_seed(noise_seed, its index in `molecules`): its samples do not depend on start /
-    end; noise_seed=None draws one from torch's CPU generator.  kw goes to node_adj_PC_generation (num_steps, max_iters, snr,
-    ...).  Returns the list of records (record_from_sample); out_path: a directory (the pickle is written into it under the
-    name "3D_to_2D_{start}_{end}_repeat_{num_repeat}") or a file path."""
+                                 molecules_per_launch=1, **kw):
+    """The 3D->2D inference script's test-set loop: num_repeat samples for every molecule of molecules[start:end].
+    molecules_per_launch=1 (the default): one sampler_3d2d.generate_2d_from_3d call per molecule.  molecules_per_launch > 1:
+    that many molecules share each reverse-SDE trajectory (sampler_3d2d.generate_2d_from_3d_grouped on
+    csrc/dense_pc_grouped.hip: per-molecule corrector statistics and noise seeds, so a molecule's samples do not depend on the
+    chunking up to the score networks' rounding), and every record carries `diverged`: True where the
+    trajectory left the finite numbers for that molecule (the others of its launch are not affected).  Either way a
+    molecule's noise seed is sampler.group_seed(noise_seed, its index in `molecules`): its samples do not depend on start /
+    end; noise_seed=None draws one from torch's CPU generator.  kw goes to node_adj_PC_generation[_grouped] (num_steps,
+    max_iters, snr, ...).  Returns the list of records (record_from_sample); out_path: a directory (the pickle is written into
+    it under the name "3D_to_2D_{start}_{end}_repeat_{num_repeat}") or a file path."""
     from .sampler import group_seed
-    from .sampler_3d2d import generate_2d_from_3d
+    from .sampler_3d2d import generate_2d_from_3d, generate_2d_from_3d_grouped
     if num_repeat < 1:
         raise ValueError("num_repeat must be at least 1")
+    chunks = launch_chunks(start, end, len(molecules), molecules_per_launch)
     name = "3D_to_2D_{}_{}_repeat_{}".format(start, end, num_repeat)
     start, end = max(0, int(start)), min(int(end), len(molecules))
     if noise_seed is None:
         noise_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     records = []
-    for i in range(start, end):
-        x, adj, _, _ = generate_2d_from_3d(model_3d, sde_model, molecules[i], num_repeat=num_repeat,
-                                           noise_seed=group_seed(noise_seed, i), **kw)
-        records.append(record_from_sample(molecules[i], x, adj))
+    if int(molecules_per_launch) == 1:
+        for i in range(start, end):
+            x, adj, _, _ = generate_2d_from_3d(model_3d, sde_model, molecules[i], num_repeat=num_repeat,
+                                               noise_seed=group_seed(noise_seed, i), **kw)
+            records.append(record_from_sample(molecules[i], x, adj))
+    else:
+        for idx in chunks:
+            samples, bad = generate_2d_from_3d_grouped(model_3d, sde_model, [molecules[i] for i in idx], num_repeat,
+                                                       [group_seed(noise_seed, i) for i in idx], **kw)
+            bad = bad.cpu().tolist()
+            for k, i in enumerate(idx):
+                rec = record_from_sample(molecules[i], samples[k][0], samples[k][1])
+                rec.diverged = bool(bad[k])
+                records.append(rec)
     if out_path is not None:
         path = os.path.join(out_path, name) if os.path.isdir(out_path) else out_path
         with open(path, "wb") as fout:
