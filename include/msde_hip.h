@@ -1192,6 +1192,51 @@ int msde_conf_rmsd_matrix_sym(const float* ref_pos, const float* gen_pos, const 
                               long long n_tiles, const unsigned char* atom_mask, long long n_conf, const long long* sym,
                               const int* perms, int lds_atoms, double* prep, double* rmsd, void* stream);
 
+/* Distance-distribution MMD of the generated against the reference conformers (csrc/conformer_mmd.hip; DESIGN 7.13: the
+ * definition is this project's).  ref_pos, gen_pos, atom_mask and n_conf as above.
+ *   mol [G][8] int64 (device): n, R, K, ref_row0, gen_row0, z_off (first element of the molecule's table in z = sum over the
+ *     molecules before it of (R + K) E), atom_off (its first atom in atom_mask), conf_off (as above).  R, K >= 1.
+ *   pair_ptr [G + 1] int64 (device), pairs [sum E][2] int32 (device): molecule g evaluates the E = pair_ptr[g + 1] -
+ *     pair_ptr[g] atom pairs pairs[pair_ptr[g] ..] = (u, v), molecule-local atom indices in [0, n), both on atoms the mask
+ *     keeps; E = 0 is allowed.  The host's duty, as for `mol`.
+ * A conformer with a non-finite coordinate on an atom the mask keeps is EXCLUDED: it takes part in no sum and no count;
+ * R' and K' are the references and generated conformers that remain, C' = R' + K', pooled with the references first.
+ * msde_conf_dist_table:
+ *   finite [n_conf] uint8: 1 for a kept conformer (records in the order of conf_off: a molecule's references, then its
+ *     generated conformers); rank [n_conf] int32: its position among the kept ones of its molecule, -1 if excluded;
+ *   used [G][2] int32 = R', K';
+ *   z fp64, column-major per molecule with leading dimension C = R + K: z[z_off + e C + rank] = |pos[u_e] - pos[v_e]|,
+ *     differences, squares and root in fp64 from the fp32 coordinates.  One distance's C' samples are contiguous; rows
+ *     C' .. C - 1 of a column are not written.
+ * msde_conf_mmd_subsets: for a set S of columns, L_ab = sum_{e in S} (z[a, e] - z[b, e])^2, sigma^2 = sum_{a, b} L_ab /
+ *   (C'^2 - C'), k(a, b) = sum_{i < kernel_num} exp(-L_ab / (sigma^2 kernel_mul^(i - kernel_num / 2))) (integer division),
+ *   MMD(S) = mean_{a, b in ref} k + mean_{a, b in gen} k - 2 mean_{a in ref, b in gen} k, diagonals included.
+ *   items [n_items][3] int32 (device) = molecule, e, f: S = {e, f}, or {e} when f = -1; the first n_cols = sum E items are
+ *     the Single items in column order (item pair_ptr[g] + e is {e} of molecule g), then molecule g's Pair items are items
+ *     n_cols + pairitem_ptr[g] .. n_cols + pairitem_ptr[g + 1] (pairitem_ptr [G + 1] int64, device).
+ *   colsum [n_cols] fp64 (written): sum_{a, b} (z[a, e] - z[b, e])^2 of every column, formed from the differences (identical
+ *     samples: exactly 0); an item's sigma^2 is the sum of its columns' entries over C'^2 - C'.
+ *   mmd [n_items] fp64: one wavefront per item, its columns staged in LDS, the pairs a < b evaluated (k is symmetric and
+ *     k(a, a) = kernel_num); L, sigma^2 and the exponent in fp64, the exponential itself in fp32, sums in fp64: per lane, then
+ *     an xor butterfly -- a fixed order, no atomics, so an item's value depends on its columns, R', K' and the kernel
+ *     parameters alone, bitwise.  R' = 0 or K' = 0: NaN.  sigma^2 = 0: exactly 0.
+ *   means [G][2] fp64: the mean of the molecule's Single items and of its Pair items (NaN without an item).
+ *   c_max = the largest R + K of the launch, 2 .. 1024 (it sizes the LDS: 32 c_max bytes per workgroup); above: MSDE_EUNSUP.
+ *   kernel_mul > 0, kernel_num in 1 .. 16 (else MSDE_EINVAL).  exp_path 0: with kernel_mul = 2 one exponential at the widest
+ *     scale and kernel_num - 1 squarings (exp(-L / s)^2 = exp(-L / (s / 2))), any other kernel_mul kernel_num exponentials;
+ *     exp_path 1: kernel_num exponentials always.
+ * msde_conf_mmd_all: all_mmd [G] fp64 = MMD over all E columns of the molecule, one workgroup each, L summed in column
+ *   order; colsum as written by msde_conf_mmd_subsets on the same table.  E = 0, R' = 0 or K' = 0: NaN. */
+int msde_conf_dist_table(const float* ref_pos, const float* gen_pos, const long long* mol, int G,
+                         const unsigned char* atom_mask, long long n_conf, const long long* pair_ptr, const int* pairs,
+                         unsigned char* finite, int* rank, int* used, double* z, void* stream);
+int msde_conf_mmd_subsets(const double* z, const long long* mol, int G, const long long* pair_ptr, long long n_cols,
+                          const int* used, const int* items, long long n_items, const long long* pairitem_ptr, int c_max,
+                          double kernel_mul, int kernel_num, int exp_path, double* colsum, double* mmd, double* means,
+                          void* stream);
+int msde_conf_mmd_all(const double* z, const long long* mol, int G, const long long* pair_ptr, const int* used,
+                      const double* colsum, double kernel_mul, int kernel_num, int exp_path, double* all_mmd, void* stream);
+
 /* ------------------------------------------------------------------ 2D graph evaluation ---- */
 /* Decoding and scoring of the 3D->2D sampler's output (class scores x, adjacency values around `bond type + 1`) against the
  * graph the 3D input came from; csrc/graph2d_eval.hip.  A launch holds G molecules; molecule g has n atoms and K samples.

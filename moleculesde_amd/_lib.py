@@ -10,6 +10,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmsde_hip.so")
 P = ctypes.c_void_p
 I = ctypes.c_int
 F = ctypes.c_float
+D = ctypes.c_double
 LL = ctypes.c_longlong
 ULL = ctypes.c_ulonglong
 
@@ -197,6 +198,9 @@ SIGNATURES = {
     "msde_conf_rmsd_matrix": [P, P, P, I, P, LL, P, LL, P, P, P],
     "msde_conf_rmsd_matrix_sym": [P, P, P, I, P, LL, P, LL, P, P, I, P, P, P],
     "msde_conf_cov_mat": [P, P, I, P, I, P, P, P],
+    "msde_conf_dist_table": [P, P, P, I, P, LL, P, P, P, P, P, P, P],
+    "msde_conf_mmd_subsets": [P, P, I, P, LL, P, P, LL, P, I, D, I, I, P, P, P, P],
+    "msde_conf_mmd_all": [P, P, I, P, P, P, D, I, I, P, P],
     "msde_graph2d_decode": [P, P, P, P, P, P, P, I, LL, I, I, I, P, P, P, P],
     "msde_graph2d_summary": [P, P, P, P, P, I, P, P, P],
     "msde_chunk_elems": [],

@@ -15,7 +15,7 @@ LIB = os.path.join(CSRC, "libmsde_hip.so")
 SOURCES = ["graph.hip", "gin.hip", "schnet.hip", "cfconv_fused.hip", "cfconv_fused_bwd.hip", "cfconv_pair.hip",
            "sde2d3d.hip", "linear.hip", "gemm_ex.hip", "gemm_rs.hip", "gemm_t2.hip", "gemm_t2_a1.hip", "gemm_t2_a2.hip", "dense_head.hip", "dense_pc.hip", "dense_pc_grouped.hip", "plan.hip", "dd.hip", "norm.hip",
            "contrastive.hip", "contrastive_infonce.hip", "optim.hip", "pointwise.hip", "gat_tail.hip", "escore_mol.hip", "escore_mol_bwd.hip",
-           "molnet_head.hip", "qm9_head.hip", "md17.hip", "dataset.hip", "conformer_rmsd.hip", "graph2d_eval.hip"]
+           "molnet_head.hip", "qm9_head.hip", "md17.hip", "dataset.hip", "conformer_rmsd.hip", "conformer_mmd.hip", "graph2d_eval.hip"]
 HEADERS = [os.path.join(CSRC, "msde_common.h"), os.path.join(CSRC, "gemm_rs.h"), os.path.join(CSRC, "gemm_rs_epi.h"), os.path.join(CSRC, "gemm_t2.h"), os.path.join(CSRC, "escore_mol.h"),
            os.path.join(HERE, "..", "include", "msde_hip.h")]
 
